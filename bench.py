@@ -1,8 +1,15 @@
 """Benchmark: CT-CLIP contrastive train step on MI355X (BASELINE.json metric: CT-report pairs/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU over RCCL -- under torch.distributed.run, or, when started without a
     launcher, bench.py starts torch.distributed.run --nproc-per-node N itself as a child process)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure and
+the in-step HIP-event figures of the same K steps).  --full adds the measurements that take runs of
+their own after the timed region: the precise image-tower modes (precise_split_tower /
+precise_f32_tower), the eval-mode forward (vit_forward_eval) and the CPU oracle baseline
+(cpu_baseline); --no-precise / --no-eval-forward / --no-cpu-baseline drop one of them from a --full
+run.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 A step = CTCLIP forward (BERT-base text tower on 128-token reports + CTViT base image tower on
 int16-HU 240x480x480 volumes + projections + InfoNCE over the all-gathered global batch) ->
@@ -42,7 +49,12 @@ def parse():
     ap.add_argument('--fp8', action='store_true',
                     help='configs[3]: the 3D-ViT forward linears as MX-fp8 GEMMs (default batch 16 per GPU)')
     ap.add_argument('--text-len', type=int, default=128)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the measurements beside the headline figure: the precise image-tower modes, '
+                         'the eval-mode forward and the CPU oracle baseline (each after the timed steps)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
     ap.add_argument('--f32-tower', action='store_true',
                     help="run the whole bench in the f32 image-tower mode (= --vit-precision f32)")
     ap.add_argument('--vit-precision', default=None, choices=['bf16', 'f32', 'split'],
@@ -68,6 +80,35 @@ def synthetic_inputs(B, L, rank, device, frames=240, size=480, vocab=30522):
     ids[:, -1] = 3
     mask = torch.ones(B, L, dtype=torch.long, device=device)
     return hu, types.SimpleNamespace(input_ids=ids, attention_mask=mask)
+
+
+DUMP_SAMPLE = 1 << 22    # elements kept of an array larger than this (16 MB each as float32)
+
+
+def dump_outputs(out_dir, loss, trainer, model):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32
+    <out_dir>/<name>.npy (3 arrays of at most DUMP_SAMPLE elements + 3 small ones, under 50 MB in all):
+    the loss train_step returned, the gradient norm and clip coefficient, the parameter arena, Adam's
+    first moment (the step's clipped gradients), the EMA codebook and the last step's VQ indices.  An
+    array larger than DUMP_SAMPLE elements is sampled at fixed positions (seeded, sorted, the same for
+    every run of the same model), so two builds are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def take(t):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator()
+            g.manual_seed(t.numel())
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        return t.float().cpu().numpy()
+
+    vq = model.visual_transformer.vq
+    arrays = {'loss': loss, 'grad_norm_clip_coef': trainer.norm, 'params': trainer.flat.data,
+              'adam_m': trainer.m, 'vq_codebook': vq.codebook, 'vq_indices': vq.state.last_indices}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), take(t))
 
 
 def cpu_baseline(batch, runs=3):
@@ -216,6 +257,9 @@ def main():
     args = parse()
     if args.batch is None:
         args.batch = 16 if args.fp8 else 8
+    if not args.full:
+        # a plain run measures the headline figure only; the legs with runs of their own need --full
+        args.no_precise = args.no_eval_forward = args.no_cpu_baseline = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         launch_ranks(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -294,6 +338,8 @@ def main():
     # every warm-up and timed step's LayerNorm-exchange status was checked by the trainer (before
     # the f32-mode steps below add theirs)
     ln_checked = trainer.ln_steps_checked
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, trainer, model)
     precise_entries = {}
     modes = {
         # the SURVEY 8(c) contract modes (precise.py): the loss the step differentiates from an
