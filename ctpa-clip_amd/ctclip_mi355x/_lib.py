@@ -126,6 +126,19 @@ class ResampleArgs(ctypes.Structure):
     ]
 
 
+class ClipLossExArgs(ctypes.Structure):
+    """ctclip_clip_loss_ex_args (include/ctclip_hip.h): the general contrastive loss."""
+    _fields_ = [
+        ('t_raw', c_vp), ('i_raw', c_vp), ('t_extra', c_vp), ('i_extra', c_vp), ('log_temp', c_vp),
+        ('Vt', c_i32), ('Vi', c_i32), ('Bg', c_i32), ('Dl', c_i32),
+        ('decoupled', c_i32), ('w_main', c_f32), ('w_multiview', c_f32),
+        ('loss', c_vp), ('pair_loss', c_vp),
+        ('dt_raw', c_vp), ('di_raw', c_vp), ('dt_extra', c_vp), ('di_extra', c_vp),
+        ('dlogtemp', c_vp),
+        ('ws', c_vp), ('ws_floats', c_i64),
+    ]
+
+
 # name -> argtypes (restype is always int32)
 _SIGS = {
     'ctclip_version': [],
@@ -238,6 +251,8 @@ _SIGS = {
     'ctclip_vq_ema_finalize_reset': [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp],
     'ctclip_vq_ema_finalize_guard': [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     'ctclip_clip_loss': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'ctclip_clip_loss_ex': [ctypes.POINTER(ClipLossExArgs), c_vp],
+    'ctclip_clip_loss_ex_ws_floats': [ctypes.POINTER(ClipLossExArgs)],
     'ctclip_clip_scores': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp],
     'ctclip_zero_shot': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],

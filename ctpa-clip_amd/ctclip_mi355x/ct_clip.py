@@ -1,9 +1,17 @@
 """CTCLIP (ct_clip/ct_clip.py:407-901) — drop-in constructor / forward signature and state_dict
 layout, with the image tower, text tower, projections and InfoNCE running on HIP kernels.
 
-Supported configuration = the one the reference trains (pretrained_model.py:31-42):
-external image / text encoders, use_mlm=False, use_visual_ssl=False, use_all_token_embeds=False,
-downsample_image_embeds=False, no multiview augmentation.  Anything else raises.
+Supported configuration = the one the reference trains (pretrained_model.py:31-42): external
+image / text encoders, use_mlm=False, use_visual_ssl=False, use_all_token_embeds=False,
+downsample_image_embeds=False -- plus the reference's three loss options that run with external
+encoders: decoupled_contrastive_learning (ct_clip.py:865-867), extra_latent_projection (CLOOB,
+:780-790,:848-849: the image -> text direction, ``text_to_image=False`` scores and the 4-tuple of
+``return_latents`` use to_text_latent_extra / to_visual_latent_extra) and image multiview
+(``aug_image=``, :663-675,:882-899).  The plain configuration runs ``functional.ClipLossFn`` on the
+one-workgroup kernel as before; any of the three options switches the loss to
+``functional.ClipLossExFn`` (one workgroup per view pair + a fixed-order reduction).
+``aug_text`` (the reference itself cannot run it: it calls ``.shape`` on a BatchEncoding) and
+everything else raises.
 """
 from __future__ import annotations
 
@@ -65,7 +73,7 @@ class CTCLIP(nn.Module):
                  multiview_loss_weight=0.1, checkpoint_during_training=False, **kwargs):
         super().__init__()
         unsupported = dict(use_all_token_embeds=use_all_token_embeds, downsample_image_embeds=downsample_image_embeds,
-                           decoupled_contrastive_learning=decoupled_contrastive_learning, use_mlm=use_mlm,
+                           use_mlm=use_mlm,
                            use_visual_ssl=use_visual_ssl or visual_ssl is not None,
                            text_causal_mask=text_causal_mask)
         bad = [k for k, v in unsupported.items() if v]
@@ -83,13 +91,17 @@ class CTCLIP(nn.Module):
         self.to_visual_latent = nn.Linear(dim_image, dim_latent, bias=False)
         self.temperature = nn.Parameter(torch.tensor(1.))
         self.extra_latent_projection = extra_latent_projection
+        self.decoupled_contrastive_learning = decoupled_contrastive_learning
         self.to_text_latent_extra = copy.deepcopy(self.to_text_latent)
         self.to_visual_latent_extra = copy.deepcopy(self.to_visual_latent)
         self.multiview_loss_weight = multiview_loss_weight
-        self._wvis = (None, None)
+        self._wvis = {}                      # bf16 casts of the visual projections, a slot per weight
         self.defer_text_backward = False     # set by CTClipTrainer (see encode)
         self._deferred_text = None
         self._deferred_image = None
+        self._deferred_text_extra = None     # the same for the extra (CLOOB) projections' latents
+        self._deferred_image_extra = None
+        self._extra_raw = (None, None)       # encode's raw extra latents (extra_latent_projection)
         self._t_gather = None
         self.ema_after_step = False          # set by CTClipTrainer.train_step (DEFER_EMA '2')
 
@@ -129,9 +141,10 @@ class CTCLIP(nn.Module):
             vqs.flush_ema()
 
     def _visual_weight_bf16(self, W):
-        """bf16 to_visual_latent weight (151 M parameters): the Adam-kept shadow when W trains,
-        else a cast cached until W changes.  Frozen in the fine-tune configuration
-        (fine_tuning_ctclip.py:6-14), so it is cast once, not every step (0.23 ms per recast)."""
+        """bf16 to_visual_latent (or to_visual_latent_extra) weight (151 M parameters): the Adam-kept
+        shadow when W trains, else a cast cached until W changes (one cache slot per weight).  Frozen
+        in the fine-tune configuration (fine_tuning_ctclip.py:6-14), so it is cast once, not every
+        step (0.23 ms per recast)."""
         from . import kernels as K
         from . import functional as Fn
         sh = Fn.shadow_bf16(W)
@@ -140,19 +153,24 @@ class CTCLIP(nn.Module):
         # only an optimizer arena member is written behind torch's version counter (raw pointers)
         in_arena = getattr(W, '_ctclip_flat', None) is not None
         key = (W.data_ptr(), W._version, K.weights_epoch() if in_arena else -1)
-        if self._wvis[0] != key:
-            self._wvis = (key, K.cast_bf16(W.detach().contiguous()))
-        return self._wvis[1]
+        slot = 'extra' if W is self.to_visual_latent_extra.weight else 'main'
+        if self._wvis.get(slot, (None, None))[0] != key:
+            self._wvis[slot] = (key, K.cast_bf16(W.detach().contiguous()))
+        return self._wvis[slot][1]
 
     def _project(self, W, Wb, pooled, pooled_b):
         # (in the f32 image-tower mode ImageProjFn's forward is the exact-f32 product, precise.py)
         return Fn.ImageProjFn.apply(pooled, pooled_b, W, Wb)
 
-    def encode(self, text, image, gather=False):
+    def encode(self, text, image, gather=False, stack=False):
         """Text + image towers and raw latents: (enc_text (B,L,768), pooled (B, h*w*d),
         text_raw (B, dl), image_raw (B, dl)).  ``gather``: the caller will compute the global-batch
         loss, so under torch.distributed the text latents' all-gather starts here (every rank makes
-        the same call); other callers (scores, encodings) issue no collective."""
+        the same call); other callers (scores, encodings) issue no collective.  ``stack``: that loss
+        is ``ClipLossExFn``, whose gathers are view stacks (the extra text latents ride the same
+        collective).  With ``extra_latent_projection`` the raw latents of to_text_latent_extra /
+        to_visual_latent_extra are left in ``self._extra_raw``.  ``image`` may hold several views
+        concatenated on the batch axis (forward's ``aug_image``)."""
         # The host queues the image tower first (its ~16 ms of GPU work keep this stream busy while
         # the host queues BERT's many small launches), BERT on the text stream (streams.py) ordered
         # only after an event taken before the image tower, so the two run side by side.
@@ -178,13 +196,24 @@ class CTCLIP(nn.Module):
                                              ready=ready)[0]
         ts = streams.text_stream(dev)
         with torch.cuda.stream(ts) if ts is not None else _nullctx():
-            t_raw = Fn.TextProjFn.apply(enc_text[:, 0, :].contiguous(), self.to_text_latent.weight)
+            cls = enc_text[:, 0, :].contiguous()
+            t_raw = Fn.TextProjFn.apply(cls, self.to_text_latent.weight)
+            t_extra = Fn.TextProjFn.apply(cls, self.to_text_latent_extra.weight) if self.extra_latent_projection else None
             # N > 1: the text latents' all-gather goes out from the text stream now, beside the
             # 3D-ViT forward still running on the main stream (SURVEY 8(e) overlap)
-            self._t_gather = dist_sync.start_gather(t_raw) if gather and dist_sync.world_rank()[0] > 1 else None
+            self._t_gather = None
+            if gather and dist_sync.world_rank()[0] > 1:
+                if stack:
+                    sets = [t_raw[None]] + ([t_extra[None]] if t_extra is not None else [])
+                    self._t_gather = dist_sync.start_gather_stacks(sets)
+                else:
+                    self._t_gather = dist_sync.start_gather(t_raw)
         streams.join_text(dev)
         if ts is not None:
             t_raw.record_stream(torch.cuda.current_stream(dev))
+            if t_extra is not None:
+                t_extra.record_stream(torch.cuda.current_stream(dev))
+        self._deferred_text_extra = self._deferred_image_extra = None
         if self.defer_text_backward and torch.is_grad_enabled() and t_raw.requires_grad:
             # the trainer back-propagates the text tower AFTER the loss / 3D-ViT graph
             # (CTClipTrainer.forward_backward): the long ViT chain is queued first, and BERT's
@@ -197,8 +226,22 @@ class CTCLIP(nn.Module):
                     d[2] = torch.cuda.current_stream(dev).record_event()
                 leaf.register_hook(mark)
             t_raw = leaf
+        if self.defer_text_backward and torch.is_grad_enabled() and t_extra is not None and t_extra.requires_grad:
+            # the extra projection's latents are cut the same way; backward_deferred_text walks
+            # BERT once from both
+            xleaf = t_extra.detach().requires_grad_(True)
+            dx = self._deferred_text_extra = [t_extra, xleaf, None]
+            if ts is not None:
+                def mark_x(g):
+                    dx[2] = torch.cuda.current_stream(dev).record_event()
+                xleaf.register_hook(mark_x)
+            t_extra = xleaf
         W = self.to_visual_latent.weight
         i_raw = self._project(W, self._visual_weight_bf16(W), pooled, pooled_b)
+        i_extra = None
+        if self.extra_latent_projection:
+            Wx = self.to_visual_latent_extra.weight
+            i_extra = self._project(Wx, self._visual_weight_bf16(Wx), pooled, pooled_b)
         if DEFER_EMA == '1' or (DEFER_EMA in ('2', '3') and not self.ema_after_step):
             self.flush_ema()               # the codebook EMA, after the projection
         if self.defer_text_backward and torch.is_grad_enabled() and i_raw.requires_grad:
@@ -207,60 +250,101 @@ class CTCLIP(nn.Module):
             ileaf = i_raw.detach().requires_grad_(True)
             self._deferred_image = [i_raw, ileaf]
             i_raw = ileaf
+        if self.defer_text_backward and torch.is_grad_enabled() and i_extra is not None and i_extra.requires_grad:
+            xileaf = i_extra.detach().requires_grad_(True)
+            self._deferred_image_extra = [i_extra, xileaf]
+            i_extra = xileaf
+        self._extra_raw = (t_extra, i_extra)
         return enc_text, pooled, t_raw, i_raw
 
     def forward(self, text, image, device=None, return_loss=False, return_encodings=False, return_latents=False,
                 freeze_image_encoder=False, freeze_text_encoder=False, text_to_image=True, aug_text=None,
                 aug_image=None):
-        """``CTCLIP.forward`` (ct_clip/ct_clip.py:614-901)."""
-        if aug_text is not None or aug_image is not None:
+        """``CTCLIP.forward`` (ct_clip/ct_clip.py:614-901).  ``aug_image``: a tensor or a tuple of
+        tensors shaped like ``image`` (int16 HU or f32), extra views of the same volumes: all views go
+        through the image tower in one call (the VQ EMA sees them all, as in the reference) and each
+        view's contrastive loss is mixed in with ``multiview_loss_weight`` (:882-899)."""
+        if aug_text is not None:
             raise NotImplementedError('multiview augmentation is off in the reference configuration')
-        if self.extra_latent_projection:
-            raise NotImplementedError('extra_latent_projection (CLOOB) is off in the reference configuration')
+        n_views = 1
+        if aug_image is not None:
+            aug = tuple(aug_image) if isinstance(aug_image, (tuple, list)) else (aug_image,)
+            assert all(a.shape == image.shape and a.dtype == image.dtype for a in aug), \
+                'every augmented view has the shape and dtype of image'
+            n_views = len(aug) + 1
+            image = torch.cat((image, *aug), dim=0)
+        is_multiview = n_views > 1
+        assert not (not return_loss and is_multiview), 'do not pass in augmented texts or images if not training'
+        assert not (self.multiview_loss_weight == 0 and is_multiview), \
+            'multiview loss weight cannot be 0 if augmented text or images passed in'
+        extra = self.extra_latent_projection
         if return_latents:
             enc_text = self.text_transformer(text.input_ids, attention_mask=text.attention_mask)[0]
             tokens = self.visual_transformer(image, return_encoded_tokens=True)
             pooled, pooled_b = self._pool_tokens(tokens)
-            t_raw = Fn.TextProjFn.apply(enc_text[:, 0, :].contiguous(), self.to_text_latent.weight)
+            cls = enc_text[:, 0, :].contiguous()
+            t_raw = Fn.TextProjFn.apply(cls, self.to_text_latent.weight)
             W = self.to_visual_latent.weight
             i_raw = self._project(W, self._visual_weight_bf16(W), pooled, pooled_b)
+            if extra:      # ct_clip.py:789-790: the 4-tuple, no tokens
+                Wx = self.to_visual_latent_extra.weight
+                t_extra = Fn.TextProjFn.apply(cls, self.to_text_latent_extra.weight)
+                i_extra = self._project(Wx, self._visual_weight_bf16(Wx), pooled, pooled_b)
+                return l2norm(t_raw), l2norm(i_raw), l2norm(t_extra), l2norm(i_extra)
             return l2norm(t_raw), l2norm(i_raw), tokens
         self._t_gather = None
-        enc_text, pooled, t_raw, i_raw = self.encode(text, image, gather=return_loss and not return_encodings)
+        # the plain configuration keeps the one-workgroup loss (ClipLossFn); any option takes ClipLossExFn
+        general = extra or self.decoupled_contrastive_learning or is_multiview
+        enc_text, pooled, t_raw, i_raw = self.encode(text, image, gather=return_loss and not return_encodings,
+                                                     stack=general)
+        (t_extra, i_extra), self._extra_raw = self._extra_raw, (None, None)
         if return_encodings:
             return enc_text, pooled
         if not return_loss:
             from . import kernels as K
+            if extra and not text_to_image:     # ct_clip.py:806: the image -> text latents
+                t_raw, i_raw = t_extra, i_extra
             return K.clip_scores(t_raw.contiguous(), i_raw.contiguous(), self.temperature.detach().reshape(1))
         tg, self._t_gather = self._t_gather, None
-        return Fn.ClipLossFn.apply(t_raw, i_raw, self.temperature, None, tg)
+        if not general:
+            return Fn.ClipLossFn.apply(t_raw, i_raw, self.temperature, None, tg)
+        B, Dl = t_raw.shape
+        w_mv = float(self.multiview_loss_weight) if is_multiview else 0.0   # ct_clip.py:886-890 (MLM / SSL weights 0)
+        return Fn.ClipLossExFn.apply(t_raw.view(1, B, Dl), i_raw.view(n_views, B, Dl),
+                                     t_extra.view(1, B, Dl) if extra else None,
+                                     i_extra.view(n_views, B, Dl) if extra else None, self.temperature,
+                                     bool(self.decoupled_contrastive_learning), 1.0 - w_mv, w_mv, None, tg)
 
     def backward_deferred_text(self):
         """Back-propagate the text tower whose graph ``encode`` detached (defer_text_backward).
         On the text stream, after the event the loss's backward recorded for its gradient: the
         autograd engine then sees producer and consumer on the same stream and adds no wait on the
-        main stream (which would serialise BERT after the whole 3D-ViT backward)."""
-        d, self._deferred_text = self._deferred_text, None
-        if d is None or d[1].grad is None:
+        main stream (which would serialise BERT after the whole 3D-ViT backward).  With the extra
+        projection both latent sets' gradients go back in one walk."""
+        ds = (self._deferred_text, self._deferred_text_extra)
+        self._deferred_text = self._deferred_text_extra = None
+        ds = [d for d in ds if d is not None and d[1].grad is not None]
+        if not ds:
             return
-        t_raw, leaf, ev = d
-        g = leaf.grad
-        ts = streams.text_stream(g.device)
-        if ts is None or ev is None:
-            torch.autograd.backward(t_raw, g)
+        roots, grads, evs = [d[0] for d in ds], [d[1].grad for d in ds], [d[2] for d in ds]
+        ts = streams.text_stream(grads[0].device)
+        if ts is None or any(ev is None for ev in evs):
+            torch.autograd.backward(roots, grads)
             return
-        ts.wait_event(ev)
-        g.record_stream(ts)
+        for ev, g in zip(evs, grads):
+            ts.wait_event(ev)
+            g.record_stream(ts)
         with torch.cuda.stream(ts):
-            torch.autograd.backward(t_raw, g)
+            torch.autograd.backward(roots, grads)
 
     def backward_deferred_image(self):
         """Back-propagate the image tower whose graph ``encode`` detached (after BERT's, see
         CTClipTrainer.forward_backward), on the current stream."""
-        d, self._deferred_image = self._deferred_image, None
-        if d is None or d[1].grad is None:
-            return
-        torch.autograd.backward(d[0], d[1].grad)
+        ds = (self._deferred_image, self._deferred_image_extra)
+        self._deferred_image = self._deferred_image_extra = None
+        ds = [d for d in ds if d is not None and d[1].grad is not None]
+        if ds:
+            torch.autograd.backward([d[0] for d in ds], [d[1].grad for d in ds])
 
     def grad_buckets(self, text_first=True):
         """Gradient all-reduce buckets in the order the backward finalises them (dist_sync): BERT's
@@ -273,7 +357,9 @@ class CTCLIP(nn.Module):
         vit = [('vit_temporal', list(vt.enc_temporal_transformer.parameters())),
                ('vit_spatial', list(vt.enc_spatial_transformer.parameters())),
                ('vit_rest', list(vt.parameters()))]
-        head = [('head', list(self.parameters()))]
+        # the scalar temperature last: the arena is packed, and a 1-element parameter ahead of the
+        # projections would leave their bf16 shadows off the 16-byte alignment the skinny GEMM needs
+        head = [('head', sorted(self.parameters(), key=lambda p: p.numel() % 8 != 0))]
         return text + vit + head if text_first else vit + text + head
 
     def _pool_tokens(self, tokens):

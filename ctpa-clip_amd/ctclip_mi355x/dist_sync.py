@@ -8,6 +8,8 @@ local batch.  Here the step has exactly three exchanges, each one collective:
      GLOBAL batch as negatives (the text latents' gather is issued on the text stream as soon as
      BERT finishes, beside the 3D-ViT forward: ``start_gather``) (every rank then computes the same global loss; ``local_rows``
      keeps the gradient rows of this rank's pairs);
+     with a loss option on (multiview / extra projection / DCL: ``ClipLossExFn``) the sets are
+     [V, B, 512] view stacks gathered per view (``gather_stacks`` / ``start_gather_stacks``);
   2. ``sum_codebook_stats``: SUM of the VQ EMA statistics (per-code counts and token sums) so every
      rank applies the same codebook update (vector_quantize_pytorch's EMA with a synced codebook);
   3. ``sum_grads``: ONE SUM all-reduce over the flat f32 gradient arena (trainer.FlatParams).
@@ -85,6 +87,47 @@ def local_rows(x: torch.Tensor, B: int) -> torch.Tensor:
     """This rank's B rows of a [world*B, ...] global tensor."""
     _, rank = world_rank()
     return x[rank * B:(rank + 1) * B]
+
+
+def start_gather_stacks(sets):
+    """Asynchronous all-gather of several [V_k, B, Dl] view stacks as ONE collective (their
+    concatenation along the view axis) -> handle for ``finish_gather_stacks``.  The text latents
+    and their extra (CLOOB) projection ride one collective this way (CTCLIP.encode)."""
+    views = [int(s.shape[0]) for s in sets]
+    x = sets[0] if len(sets) == 1 else torch.cat([s.detach() for s in sets], 0)
+    return start_gather(x), views
+
+
+def finish_gather_stacks(handle):
+    """The gathered stacks [V_k, world*B, Dl], one per input set: within every view the global row
+    is rank * B + b, so a pair's positives stay on the diagonal of its [world*B, world*B] matrix."""
+    h, views = handle
+    out = finish_gather(h)
+    world, _ = world_rank()
+    if world > 1:
+        V, B = sum(views), out.shape[1]
+        out = out.view(world, V, B, -1).permute(1, 0, 2, 3).reshape(V, world * B, -1)
+    return [t.contiguous() for t in out.split(views, 0)]
+
+
+def gather_stacks(text_sets, image_sets, t_handle=None):
+    """Lists of [V, B, Dl] view stacks on each rank -> the same lists gathered to [V, world*B, Dl].
+    ``t_handle``: the text sets' gather already started by ``start_gather_stacks`` (CTCLIP.encode);
+    otherwise all sets go out as one collective."""
+    world, _ = world_rank()
+    if world == 1:
+        return [t.contiguous() for t in text_sets], [t.contiguous() for t in image_sets]
+    if t_handle is not None:
+        ih = start_gather_stacks(image_sets)
+        return finish_gather_stacks(t_handle), finish_gather_stacks(ih)
+    both = finish_gather_stacks(start_gather_stacks(list(text_sets) + list(image_sets)))
+    return both[:len(text_sets)], both[len(text_sets):]
+
+
+def local_view_rows(x: torch.Tensor, B: int) -> torch.Tensor:
+    """This rank's B rows of every view of a [V, world*B, ...] global stack."""
+    _, rank = world_rank()
+    return x[:, rank * B:(rank + 1) * B]
 
 
 def replicated_grad_scale() -> float:

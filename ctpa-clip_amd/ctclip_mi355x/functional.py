@@ -1244,6 +1244,42 @@ class ClipLossFn(torch.autograd.Function):
         return dt * s, di * s, (dlt * s * ctx.scale).reshape(()), None, None
 
 
+class ClipLossExFn(torch.autograd.Function):
+    """The reference's loss options beyond the plain configuration (ct_clip/ct_clip.py:845-899):
+    image multiview pairs, the CLOOB extra latent pair for the image -> text direction and decoupled
+    contrastive learning, on the fused ``kernels.clip_loss_ex``.  ``t_raw`` [Vt, B, Dl] / ``i_raw``
+    [Vi, B, Dl] are view stacks of raw latents (view 0 the un-augmented batch), ``t_extra`` /
+    ``i_extra`` the extra pair or None.  Under torch.distributed every set is all-gathered per view
+    (global row rank * B + b within each view, so the positives stay on the diagonal), every rank
+    computes the same global loss and back-propagates its own rows, as ``ClipLossFn``."""
+
+    @staticmethod
+    def forward(ctx, t_raw, i_raw, t_extra, i_extra, log_temp, decoupled=False, w_main=1.0, w_multiview=0.0,
+                impl=None, t_gather=None):
+        B = t_raw.shape[1]
+        has_x = t_extra is not None
+        tg, ig = dist_sync.gather_stacks([t_raw, t_extra] if has_x else [t_raw],
+                                         [i_raw, i_extra] if has_x else [i_raw], t_gather)
+        # impl: the fused HIP loss (default); tests substitute a CPU restatement to exercise the
+        # exchange logic under gloo
+        loss, dt, di, dtx, dix, dlt = (impl or K.clip_loss_ex)(
+            tg[0], ig[0], log_temp.reshape(1).contiguous(), tg[1] if has_x else None, ig[1] if has_x else None,
+            decoupled, w_main, w_multiview)[:6]
+        saved = [dt, di] + ([dtx, dix] if has_x else [])
+        ctx.save_for_backward(dlt, *[dist_sync.local_view_rows(g, B) for g in saved])
+        ctx.has_x = has_x
+        ctx.scale = dist_sync.replicated_grad_scale()
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dlt, dt, di, *dx = ctx.saved_tensors
+        s = dloss.reshape(1)
+        dtx, dix = (dx[0] * s, dx[1] * s) if ctx.has_x else (None, None)
+        # the log-temperature gradient is the full global value on every rank (see ClipLossFn)
+        return dt * s, di * s, dtx, dix, (dlt * s * ctx.scale).reshape(()), None, None, None, None, None
+
+
 # ----------------------------------------------------------------------------- BERT
 class BertEmbedFn(torch.autograd.Function):
     """BertEmbeddings: word + position + token_type(0), LayerNorm(eps 1e-12)."""

@@ -1206,6 +1206,41 @@ def clip_loss(t_raw, i_raw, log_temp):
     return loss, dt, di, dlt, tn, inn, sim
 
 
+def clip_loss_ex(t_raw, i_raw, log_temp, t_extra=None, i_extra=None, decoupled=False, w_main=1.0, w_multiview=0.0):
+    """The general contrastive loss (ctclip_clip_loss_ex; ct_clip/ct_clip.py:845-899): t_raw
+    [Vt, Bg, Dl] / i_raw [Vi, Bg, Dl] raw latents, view-major, optionally the extra (CLOOB) pair of
+    the same shapes.  Returns (loss [1], dt, di, dt_extra, di_extra, dlt [1], pair_loss [Vt * Vi]);
+    the extra gradients are None without the extra pair."""
+    if t_raw.dim() != 3 or i_raw.dim() != 3 or t_raw.shape[1:] != i_raw.shape[1:]:
+        raise ValueError(f'clip_loss_ex: [views, Bg, Dl] stacks, got {tuple(t_raw.shape)} / {tuple(i_raw.shape)}')
+    if (t_extra is None) != (i_extra is None):
+        raise ValueError('clip_loss_ex: the extra latents come as a pair')
+    if t_extra is not None and (t_extra.shape != t_raw.shape or i_extra.shape != i_raw.shape):
+        raise ValueError('clip_loss_ex: the extra latents have the shapes of the main ones')
+    tens = [x if x is None else x.contiguous() for x in (t_raw, i_raw, t_extra, i_extra)]
+    if any(x is not None and x.dtype != F32 for x in tens) or log_temp.dtype != F32:
+        raise ValueError('clip_loss_ex: f32 inputs')
+    t_raw, i_raw, t_extra, i_extra = tens
+    Vt, Bg, Dl = t_raw.shape
+    Vi = i_raw.shape[0]
+    dev = t_raw.device
+    loss = torch.empty(1, device=dev, dtype=F32)
+    dlt = torch.empty(1, device=dev, dtype=F32)
+    pair = torch.empty(Vt * Vi, device=dev, dtype=F32)
+    dt, di = torch.empty_like(t_raw), torch.empty_like(i_raw)
+    dtx = torch.empty_like(t_extra) if t_extra is not None else None
+    dix = torch.empty_like(i_extra) if i_extra is not None else None
+    a = _lib.ClipLossExArgs(t_raw=ptr(t_raw), i_raw=ptr(i_raw), t_extra=ptr(t_extra), i_extra=ptr(i_extra),
+                            log_temp=ptr(log_temp), Vt=Vt, Vi=Vi, Bg=Bg, Dl=Dl, decoupled=int(bool(decoupled)),
+                            w_main=float(w_main), w_multiview=float(w_multiview), loss=ptr(loss), pair_loss=ptr(pair),
+                            dt_raw=ptr(dt), di_raw=ptr(di), dt_extra=ptr(dtx), di_extra=ptr(dix), dlogtemp=ptr(dlt))
+    n = _lib.lib().ctclip_clip_loss_ex_ws_floats(_lib.ctypes.byref(a))
+    ws = torch.empty(max(n, 1), device=dev, dtype=F32)
+    a.ws, a.ws_floats = ptr(ws), n
+    call('ctclip_clip_loss_ex', _lib.ctypes.byref(a), stream_ptr())
+    return loss, dt, di, dtx, dix, dlt, pair
+
+
 def zero_shot(t_raw, i_raw, log_temp):
     """Raw prompt latents [2P, Dl] (pairs present / not present) x raw image latents [N, Dl] ->
     (probs [N, P], scores [N, P, 2]); ct_clip/ctclip_inference.py:305-315."""

@@ -9,10 +9,12 @@ BASE_VIT = dict(dim=512, codebook_size=8192, image_size=480, patch_size=20, temp
                 spatial_depth=4, temporal_depth=4, dim_head=32, heads=8)
 
 
-def build_ctclip(vit=None, bert=None, dim_latent=512, frames=240):
+def build_ctclip(vit=None, bert=None, dim_latent=512, frames=240, **loss_options):
     """CT-CLIP as the reference assembles it.  ``vit`` = CTViT kwargs (default: base),
     ``bert`` = BertConfig (default: BERT-base as CXR-BERT-specialized).  The flattened image
-    embedding width follows from the ViT grid: (image/patch)^2 * dim (ct_clip.py:724,740)."""
+    embedding width follows from the ViT grid: (image/patch)^2 * dim (ct_clip.py:724,740).
+    ``loss_options``: CTCLIP's decoupled_contrastive_learning / extra_latent_projection /
+    multiview_loss_weight (default: the reference configuration, all off / 0.1)."""
     vk = dict(BASE_VIT)
     vk.update(vit or {})
     image_encoder = CTViT(**vk, use_vgg_and_gan=False)
@@ -21,8 +23,8 @@ def build_ctclip(vit=None, bert=None, dim_latent=512, frames=240):
     dim_image = grid * grid * vk['dim']
     return CTCLIP(image_encoder=image_encoder, text_encoder=text_encoder,
                   dim_text=text_encoder.config.hidden_size, dim_image=dim_image, dim_latent=dim_latent,
-                  extra_latent_projection=False, use_mlm=False, downsample_image_embeds=False,
-                  use_all_token_embeds=False)
+                  **{'extra_latent_projection': False, **loss_options}, use_mlm=False,
+                  downsample_image_embeds=False, use_all_token_embeds=False)
 
 
 def set_finetune_trainable(model):

@@ -11,6 +11,8 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.layernorm(x, gamma, beta, eps)
     torch.ops.ctclip.cos_attn(q, k, v, q_scale, k_scale, heads, seq_len, layout, scale, bias, grid)
     torch.ops.ctclip.clip_infonce(text_latents, image_latents, log_temp)
+    torch.ops.ctclip.clip_infonce_ex(text_views, image_views, log_temp, text_extra, image_extra,
+                                     decoupled, w_main, w_multiview)   # multiview / CLOOB / DCL loss
     torch.ops.ctclip.vq_cos_argmax(x, codebook)                 # (idx int32, l2norm(x))
     torch.ops.ctclip.peg_dwconv3d(x, weight, bias, shape, mode)  # x + PEG(x), canonical rows
     torch.ops.ctclip.cpb_mlp(rel, w0, b0, w1, b1, w2, b2)        # CPB table [heads, bins]
@@ -218,6 +220,62 @@ def clip_infonce(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor) 
     """Symmetric InfoNCE of ct_clip/ct_clip.py:796-812 on raw latents: l2-normalise both, sim =
     exp(log_temp) * t . i^T, loss = (CE(sim, arange) + CE(sim^T, arange)) / 2 (scalar)."""
     return _clip_infonce(text_latents, image_latents, log_temp)[0]
+
+
+# ------------------------------------------------------------------------ clip_infonce_ex
+@torch.library.custom_op('ctclip::clip_infonce_ex', mutates_args=(), device_types='cuda')
+def _clip_infonce_ex(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor, text_extra: Optional[Tensor],
+                     image_extra: Optional[Tensor], decoupled: bool, w_main: float,
+                     w_multiview: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    _need(text_latents.dtype == image_latents.dtype == log_temp.dtype == F32, 'clip_infonce_ex: f32 inputs')
+    _need(text_latents.dim() == 3 and image_latents.dim() == 3 and text_latents.shape[1:] == image_latents.shape[1:],
+          'clip_infonce_ex: view stacks [views, B, dim_latent]')
+    _need((text_extra is None) == (image_extra is None), 'clip_infonce_ex: the extra latents come as a pair')
+    _need(text_extra is None or (text_extra.shape == text_latents.shape and image_extra.shape == image_latents.shape
+                                 and text_extra.dtype == image_extra.dtype == F32),
+          'clip_infonce_ex: the extra latents have the shapes of the main ones (f32)')
+    _need(log_temp.numel() == 1, 'clip_infonce_ex: log_temp is a scalar')
+    loss, dt, di, dtx, dix, dlt, pair = K.clip_loss_ex(text_latents, image_latents, log_temp.reshape(1).contiguous(),
+                                                       text_extra, image_extra, decoupled, w_main, w_multiview)
+    if dtx is None:
+        dtx, dix = text_latents.new_empty(0), text_latents.new_empty(0)
+    return loss.reshape(()), dt, di, dtx, dix, dlt.reshape(log_temp.shape), pair
+
+
+@_clip_infonce_ex.register_fake
+def _(text_latents, image_latents, log_temp, text_extra, image_extra, decoupled, w_main, w_multiview):
+    has_x = text_extra is not None
+    return (text_latents.new_empty(()), torch.empty_like(text_latents), torch.empty_like(image_latents),
+            torch.empty_like(text_extra) if has_x else text_latents.new_empty(0),
+            torch.empty_like(image_extra) if has_x else text_latents.new_empty(0), torch.empty_like(log_temp),
+            text_latents.new_empty(text_latents.shape[0] * image_latents.shape[0]))
+
+
+def _clip_ex_setup(ctx, inputs, output):
+    _, dt, di, dtx, dix, dlt, _ = output
+    ctx.has_x = inputs[3] is not None
+    ctx.save_for_backward(dt, di, dtx, dix, dlt)
+
+
+def _clip_ex_bwd(ctx, dloss, *_):
+    dt, di, dtx, dix, dlt = ctx.saved_tensors
+    return (dt * dloss, di * dloss, dlt * dloss, dtx * dloss if ctx.has_x else None,
+            dix * dloss if ctx.has_x else None, None, None, None)
+
+
+_clip_infonce_ex.register_autograd(_clip_ex_bwd, setup_context=_clip_ex_setup)
+
+
+def clip_infonce_ex(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor, text_extra: Optional[Tensor] = None,
+                    image_extra: Optional[Tensor] = None, decoupled: bool = False, w_main: float = 1.0,
+                    w_multiview: float = 0.0) -> Tensor:
+    """The general contrastive loss of ct_clip/ct_clip.py:845-899 on raw latent view stacks
+    [views, B, dim_latent] (view 0 = the un-augmented batch): per (text view, image view) pair the
+    symmetric InfoNCE of ``clip_infonce``, its image -> text direction on the extra (CLOOB) pair
+    when given, the diagonal out of the denominators when ``decoupled``; the result is w_main *
+    loss of pair 0 + w_multiview * mean of the other pairs (scalar)."""
+    return _clip_infonce_ex(text_latents, image_latents, log_temp, text_extra, image_extra, bool(decoupled),
+                            float(w_main), float(w_multiview))[0]
 
 
 # -------------------------------------------------------------------------- vq_cos_argmax

@@ -227,13 +227,14 @@ class CTClipTrainer:
     def _fold_bucket(self, tag):
         self.flat.rebind_grads(self.bucket_params.get(tag, ()))
 
-    def forward_backward(self, text, video):
+    def forward_backward(self, text, video, aug_image=None):
         self.grad_sync.arm()
         defer = hasattr(self.model, 'backward_deferred_text')
         if defer:
             self.model.defer_text_backward = True
         try:
-            loss = self.model(text, video, device=self.device, return_loss=True)
+            kw = {} if aug_image is None else dict(aug_image=aug_image)   # extra image views (multiview)
+            loss = self.model(text, video, device=self.device, return_loss=True, **kw)
             loss.backward()                      # the loss node (both towers' latents are leaves)
             if defer:
                 # BERT first (text stream): its layer-group buckets go out to RCCL as its backward
@@ -392,24 +393,25 @@ class CTClipTrainer:
                skip=self.skip_ring[st % 4:st % 4 + 1] if self._guard else None)
         self.flat.sync_shadows(off, off + n)
 
-    def train_step(self, text, video):
-        """One contrastive step; returns the loss tensor (no host sync).  Raises
+    def train_step(self, text, video, aug_image=None):
+        """One contrastive step; returns the loss tensor (no host sync).  ``aug_image``: augmented
+        views of ``video`` for the multiview loss (CTCLIP.forward).  Raises
         LayerNormExchangeError once the status copy of an earlier step shows a timed-out LayerNorm
         exchange (at the latest two steps later; ``check()`` / ``flush()`` wait for all)."""
         hp = streams.main_stream(self.device)
         if hp is None:
-            return self._train_step(text, video)
+            return self._train_step(text, video, aug_image)
         # CTCLIP_MAIN_PRIORITY=1: the step on the high-priority stream, ordered after the caller's
         # work so far, and the caller's stream after it
         caller = torch.cuda.current_stream(self.device)
         hp.wait_stream(caller)
         with torch.cuda.stream(hp):
-            loss = self._train_step(text, video)
+            loss = self._train_step(text, video, aug_image)
         caller.wait_stream(hp)
         loss.record_stream(caller)
         return loss
 
-    def _train_step(self, text, video):
+    def _train_step(self, text, video, aug_image=None):
         self._check_ln(block_upto=self.steps - 2)
         self.model.train()
         own = hasattr(self.model, 'ema_after_step')
@@ -417,7 +419,7 @@ class CTClipTrainer:
             self.model.ema_after_step = True     # the codebook EMA goes after optimizer_step
         try:
             with K.ln_guard():
-                loss = self.forward_backward(text, video)
+                loss = self.forward_backward(text, video, aug_image)
         finally:
             if own:
                 self.model.ema_after_step = False

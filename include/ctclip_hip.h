@@ -626,7 +626,40 @@ int ctclip_vq_ema_finalize_guard(float* bins, int64_t* esum, int32_t C, int32_t 
 int ctclip_clip_loss(const float* t_raw, const float* i_raw, int32_t Bg, int32_t Dl, const float* log_temp,
                      float* t_norm, float* i_norm, float* loss, float* dt_raw, float* di_raw, float* dlogtemp,
                      float* sim, void* stream);
-/* eval branch einsum('b d, b d -> b') * temp (ct_clip.py:805-807) */
+/* The general contrastive loss of ct_clip/ct_clip.py:845-899: multiview pairs, the CLOOB extra latent
+ * pair for the image->text direction (:780-790,:848-849) and decoupled contrastive learning
+ * (:865-867), fused forward + backward.  t_raw [Vt][Bg][Dl] / i_raw [Vi][Bg][Dl] are raw projected
+ * latents, view-major, view 0 the un-augmented batch; t_extra / i_extra (both or neither) have the
+ * same shapes.  The P = Vt * Vi view pairs are ordered p = m * Vi + n.  For pair p, with every
+ * latent l2-normalised (eps 1e-12) and temp = exp(*log_temp):
+ *   S = temp t_m . i_n^T (text -> image);  image -> text is S^T, or temp i'_n . t'_m^T with the extra pair;
+ *   loss_p = 1/2 (mean_i(-log(pos_i + 1e-20) + log(den_i + 1e-20)) + the same for the other direction),
+ *   pos = exp(diagonal), den = row sums of exp -- without the diagonal term when decoupled != 0;
+ *   *loss = w_main loss_0 + w_multiview mean(loss_1 .. loss_{P-1})   (no max subtraction).
+ * Outputs: loss [1], pair_loss [P], dlogtemp [1], and d loss / d raw for each latent set (dt_raw,
+ * di_raw, and dt_extra / di_extra with the extra pair); a row that takes part in several pairs gets
+ * the sum over them.  One workgroup per pair writes its loss and partial gradients into ws; a second
+ * kernel sums them in ascending pair order: no float atomics, bit-reproducible.  With P = 1, no
+ * extra pair, decoupled = 0 and w_main = 1 every output equals ctclip_clip_loss's bit for bit.
+ * ws: ctclip_clip_loss_ex_ws_floats(a) floats (0 = unsupported shape).  Bg <= 128, Dl <= 8192,
+ * P <= 64: CT_ESHAPE otherwise; a missing pointer, half an extra pair or a short ws: CT_EINVAL. */
+typedef struct {
+  const float* t_raw; const float* i_raw;
+  const float* t_extra; const float* i_extra;   /* optional, both or neither */
+  const float* log_temp;
+  int32_t Vt, Vi, Bg, Dl;
+  int32_t decoupled;
+  float w_main, w_multiview;
+  float* loss; float* pair_loss;
+  float* dt_raw; float* di_raw;
+  float* dt_extra; float* di_extra;             /* required with the extra pair */
+  float* dlogtemp;
+  float* ws; int64_t ws_floats;
+} ctclip_clip_loss_ex_args;
+int ctclip_clip_loss_ex(const ctclip_clip_loss_ex_args* a, void* stream);
+int ctclip_clip_loss_ex_ws_floats(const ctclip_clip_loss_ex_args* a);
+/* eval branch einsum('b d, b d -> b') * temp (ct_clip.py:805-807); with extra_latent_projection and
+ * text_to_image = False the caller passes the extra latents (:806) */
 int ctclip_clip_scores(const float* t_raw, const float* i_raw, int32_t B, int32_t Dl, const float* log_temp,
                        float* out, void* stream);
 /* zero-shot pathology scoring, replaces the per-volume x per-pathology loop of
