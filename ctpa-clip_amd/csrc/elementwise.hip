@@ -275,9 +275,15 @@ extern "C" int ctclip_add_f32(const float* a, const float* b, float* y, void* yb
 }
 
 namespace {
+// f32 in, f32 out (nn.GELU of the f32 feature projector, vqa.py): common.h's erf_fast carries
+// 1.5e-7 ABSOLUTE error, sized for outputs stored in bf16; here it is ~2.5e-7 of an f32 result
+// (x ~ -3) and everything of the negative tail, where 1 + erf cancels.  libm's erfc keeps the
+// tail's relative accuracy: gelu(x) = x/2 erfc(-x / sqrt 2).
 __global__ __launch_bounds__(256) void gelu_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    y[i] = gelu_erf(x[i]);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = x[i];
+    y[i] = 0.5f * v * erfcf(-v * 0.70710678118654752f);
+  }
 }
 }  // namespace
 

@@ -1,7 +1,11 @@
 // Optimizer step of CTClipTrainer.train_step (ct_clip/CTCLIPTrainer.py:347-353):
-// clip_grad_norm_(max_norm) then Adam (ct_clip/optimizer.py:24, wd = 0 -> torch.optim.Adam),
-// over ONE flat f32 parameter / gradient arena, with the bf16 working copy refreshed in the
-// same pass.  Norm clip coefficient computed on device (no host sync).
+// clip_grad_norm_(max_norm) then the optimizer of ct_clip/optimizer.py:23-34 -- wd = 0:
+// torch.optim.Adam (:24); wd != 0: torch.optim.AdamW, DECOUPLED decay p *= 1 - lr wd ahead of the
+// Adam update, whose moments see the undecayed gradient -- over slices of ONE flat f32 parameter /
+// gradient arena, with the bf16 working copy refreshed in the same pass.  The reference decays only
+// parameters with ndim >= 2 (:27-32); the kernel decays every element of the slice it is given, so
+// the caller launches the ndim >= 2 slice with wd and the rest with wd = 0 (trainer.CTClipTrainer).
+// Norm clip coefficient computed on device (no host sync).
 #include "common.h"
 #include "../../include/ctclip_hip.h"
 
@@ -40,9 +44,11 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
 }
 
 __device__ __forceinline__ float adam_one(float& pi, float gi, float& mi, float& vi, float c, float b1, float b2,
-                                          float eps, float wd, float step, float bc2_sqrt) {
+                                          float eps, float decay, float step, float bc2_sqrt) {
   gi *= c;
-  if (wd != 0.f) gi += wd * pi;
+  // AdamW's decoupled decay, in torch's order: first p *= 1 - lr wd, then the Adam update from the
+  // undecayed gradient.  decay == 1 (wd = 0) leaves plain Adam, bit for bit.
+  if (decay != 1.f) pi *= decay;
   mi = b1 * mi + (1.f - b1) * gi;
   vi = b2 * vi + (1.f - b2) * gi * gi;
   pi -= step * mi / (sqrtf(vi) / bc2_sqrt + eps);
@@ -54,7 +60,7 @@ __device__ __forceinline__ float adam_one(float& pi, float gi, float& mi, float&
 // The gradient is zeroed in the same pass (the trainer's zero_grad).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, int head,
-                                                   float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                   float lr, float b1, float b2, float eps, float decay, float bc1,
                                                    float bc2_sqrt, const float* __restrict__ coef,
                                                    u16* __restrict__ pb, u16* __restrict__ pbl, int zero_grad,
                                                    const int* __restrict__ skip) {
@@ -85,7 +91,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float pj = pi[j], mj = mi[j], vj = vi[j];
-      o[j] = adam_one(pj, gi[j], mj, vj, c, b1, b2, eps, wd, step, bc2_sqrt);
+      o[j] = adam_one(pj, gi[j], mj, vj, c, b1, b2, eps, decay, step, bc2_sqrt);
       pi[j] = pj; mi[j] = mj; vi[j] = vj;
     }
     p4[i] = pi; m4[i] = mi; v4[i] = vi;
@@ -110,7 +116,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     const int64_t i = t < 4 ? (t < head ? t : -1) : head + 4 * n4 + (t - 4);
     if (i >= 0 && i < n) {
       float pj = p[i], mj = m[i], vj = v[i];
-      adam_one(pj, g[i], mj, vj, c, b1, b2, eps, wd, step, bc2_sqrt);
+      adam_one(pj, g[i], mj, vj, c, b1, b2, eps, decay, step, bc2_sqrt);
       p[i] = pj; m[i] = mj; v[i] = vj;
       if (zero_grad) g[i] = 0.f;
       if (pb) pb[i] = f2bf(pj);
@@ -140,6 +146,8 @@ extern "C" int ctclip_adam(float* p, float* g, float* m, float* v, int64_t n, fl
                            int32_t zero_grad, const int32_t* skip, void* stream) {
   const float bc1 = 1.f - powf(b1, (float)step);
   const float bc2 = sqrtf(1.f - powf(b2, (float)step));
+  // torch.optim.AdamW: param.mul_(1 - lr * weight_decay), the factor formed in double
+  const float decay = wd != 0.f ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
   if (n <= 0) return 0;
   // p, g, m, v are slices of arenas with one shared element layout: one alignment head for all
   const int head = (int)std::min<int64_t>(n, ((16 - ((uintptr_t)p & 15)) & 15) / 4);
@@ -149,7 +157,7 @@ extern "C" int ctclip_adam(float* p, float* g, float* m, float* v, int64_t n, fl
   const int64_t n4 = (n - head) / 4;
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n4 + 255) / 256));
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, head, lr, b1, b2,
-                     eps, wd, bc1, bc2, coef, (u16*)p_bf16, (u16*)p_bf16_lo, zero_grad, skip);
+                     eps, decay, bc1, bc2, coef, (u16*)p_bf16, (u16*)p_bf16_lo, zero_grad, skip);
   CT_CHECK_LAUNCH();
   return 0;
 }

@@ -181,7 +181,16 @@ def grad_buckets(model):
 class CTClipTrainer:
     """Optimiser + step for a ``ctclip_mi355x.CTCLIP``.  Hyper-parameters default to the
     reference's (CTCLIPTrainer.py:203-205, optimizer.py:24: Adam lr 1.25e-6, betas (0.9, 0.99),
-    eps 1e-8, wd 0, clip 0.5)."""
+    eps 1e-8, wd 0, clip 0.5).
+
+    ``wd`` restates ct_clip/optimizer.py:23-34.  wd == 0: torch.optim.Adam.  wd != 0:
+    torch.optim.AdamW -- decoupled decay p *= 1 - lr wd ahead of the Adam update -- on the parameters
+    with ndim >= 2 only (optimizer.py:3-8); biases, LayerNorm gains, q_scale / k_scale and the
+    temperature are not decayed.  The Adam kernel decays every element of the slice it is given, so
+    with wd != 0 every gradient bucket's parameters are stably partitioned, ndim >= 2 first (BERT's
+    q / k / v weights stay adjacent, and so do their biases: functional.bf_cat / gsink_cat), and the
+    bucket's Adam runs as two launches, the first slice with wd, the second with 0.  With wd == 0
+    the arena order and the launches are the undivided ones."""
 
     def __init__(self, model, lr=1.25e-6, wd=0.0, max_grad_norm=0.5, betas=(0.9, 0.99), eps=1e-8,
                  overlap_grad_sync=True, defer_text_adam=False):
@@ -193,13 +202,18 @@ class CTClipTrainer:
         self.device = dev
         # arena order = gradient bucket order, so every bucket is one contiguous slice
         groups = grad_buckets(model) if overlap_grad_sync else [('all', list(model.parameters()))]
+        if wd != 0:
+            # decayed (ndim >= 2) parameters first in every bucket, each kind in its old order
+            groups = [(tag, [p for p in ps if p.ndim >= 2] + [p for p in ps if p.ndim < 2]) for tag, ps in groups]
         self.flat = FlatParams([p for _, ps in groups for p in ps], dev)
         segs, off, self.bucket_params = [], 0, {}
+        self.decay_segs = []      # (offset, numel, numel of the leading ndim >= 2 slice) per bucket
         for tag, ps in groups:
             n = sum(p.numel() for p in ps if p.requires_grad)
             if n:
                 segs.append((tag, off, n))
                 self.bucket_params[tag] = [p for p in ps if p.requires_grad]
+                self.decay_segs.append((off, n, sum(p.numel() for p in ps if p.requires_grad and p.ndim >= 2)))
             off += n
         self.grad_sync = dist_sync.BucketedGradSync(self.flat.grad, segs, before_launch=self._fold_bucket,
                                                     status=(self.flat.status, self._local_status))
@@ -384,10 +398,25 @@ class CTClipTrainer:
             self.ln_steps_checked = step
 
     def _adam(self, off, n, step=None):
+        """Adam over the arena slice [off, off + n), a run of whole buckets.  wd != 0: two launches
+        per bucket, its ndim >= 2 slice with wd and the rest with 0 (optimizer.py:26-32)."""
+        if self.wd == 0:
+            return self._adam_slice(off, n, 0.0, step)
+        done = 0
+        for boff, bn, nd in self.decay_segs:
+            if off <= boff and boff + bn <= off + n:
+                if nd:
+                    self._adam_slice(boff, nd, self.wd, step)
+                if bn - nd:
+                    self._adam_slice(boff + nd, bn - nd, 0.0, step)
+                done += bn
+        assert done == n, (off, n, done)
+
+    def _adam_slice(self, off, n, wd, step=None):
         sl = slice(off, off + n)
         st = self.steps if step is None else step
         K.adam(self.flat.data[sl], self.flat.grad[sl], self.m[sl], self.v[sl], lr=self.lr, b1=self.betas[0],
-               b2=self.betas[1], eps=self.eps, wd=self.wd, step=self.steps if step is None else step, coef=self.norm,
+               b2=self.betas[1], eps=self.eps, wd=wd, step=self.steps if step is None else step, coef=self.norm,
                p_bf16=self.flat.bf16[sl] if self.flat.bf16 is not None else None,
                p_bf16_lo=self.flat.bf16_lo[sl] if self.flat.bf16_lo is not None else None, zero_grad=True,
                skip=self.skip_ring[st % 4:st % 4 + 1] if self._guard else None)

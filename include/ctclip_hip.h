@@ -689,7 +689,11 @@ int ctclip_embed_bwd(const int64_t* ids, int64_t B, int32_t L, int32_t Hd, const
 
 /* ---------------------------------------------------------------- optimizer (CTCLIPTrainer.py:347-353)
  * grad norm -> out[0] = norm, out[1] = clip coef (torch clip_grad_norm_ semantics);
- * Adam over a flat arena (optimizer.py:24), grads scaled by coef[1], bf16 copy refreshed;
+ * Adam over a slice of a flat arena, grads scaled by coef[1], bf16 copy refreshed.  wd == 0:
+ * torch.optim.Adam (optimizer.py:23-24).  wd != 0: torch.optim.AdamW (optimizer.py:34), decoupled
+ * decay in torch's order -- p *= 1 - lr wd, then the Adam update from the undecayed gradient -- on
+ * EVERY element of the slice: the reference decays only parameters with ndim >= 2 (optimizer.py:3-8,
+ * 26-32), so the caller passes wd for the slice holding those and 0 for the rest;
  * zero_grad != 0 also zeroes g in the same pass (the trainer's zero_grad, CTCLIPTrainer.py:353).
  * skip (optional device int32): when *skip != 0 the step is dropped: p, m, v unchanged, g zeroed if
  * zero_grad (the step's guard word:

@@ -348,6 +348,53 @@ def test_deferred_text_adam_matches(setup):
     assert torch.equal(p0, p1), (p0 - p1).abs().max().item()
 
 
+def test_weight_decay_decays_matrices_only(setup):
+    """CTClipTrainer(wd=...) restates the reference's get_optimizer (ct_clip/optimizer.py:23-34):
+    AdamW, decoupled, on the parameters with ndim >= 2 only.  Two fresh identical models take one
+    step at lr 1e-3, one with wd = 0 and one with wd = 0.1.  The Adam update does not see the decay,
+    so every ndim < 2 parameter is bit-equal between the two and every ndim >= 2 parameter differs
+    by -lr wd p_before (relative norm 1e-3: the difference is ~1e-4 |p|, of which p's f32 rounding
+    leaves ~1e-3).  The clip is off in both runs: its coefficient comes from a norm summed in arena
+    order, which the wd != 0 partition changes, and a last-bit change of it would reach every
+    parameter.  The bf16 shadows equal p.bfloat16() after the step in either layout."""
+    cfg, _, hu, ids, mask, text = setup
+    from ctclip_mi355x.trainer import CTClipTrainer
+    from ctclip_mi355x import functional as Fn
+    lr, wd = 1e-3, 0.1
+    runs = []
+    for w in (0.0, wd):
+        torch.manual_seed(0)
+        model = build(cfg)
+        before = {n: p.detach().clone() for n, p in model.named_parameters() if p.requires_grad}
+        tr = CTClipTrainer(model, lr=lr, wd=w, max_grad_norm=0)
+        tr.train_step(text, hu.cuda())
+        tr.flush()
+        torch.cuda.synchronize()
+        for q in tr.flat.params:
+            sh = Fn.shadow_bf16(q)
+            assert sh is not None and torch.equal(sh, q.detach().bfloat16())
+        a = model.text_transformer.encoder.layer[0].attention.self
+        assert Fn.bf_cat([a.query.weight, a.key.weight, a.value.weight]).data_ptr() == \
+            Fn.shadow_bf16(a.query.weight).data_ptr()
+        assert Fn.cat_f32([a.query.bias, a.key.bias, a.value.bias]).data_ptr() == a.query.bias.data_ptr()
+        runs.append((before, {n: p.detach().clone() for n, p in model.named_parameters() if p.requires_grad}))
+        del model, tr
+    (b0, a0), (b1, a1) = runs
+    assert b0.keys() == b1.keys() and all(torch.equal(b0[n], b1[n]) for n in b0)
+    worst, nmat, nvec = 0.0, 0, 0
+    for n in b0:
+        if b0[n].ndim < 2:
+            nvec += 1
+            assert torch.equal(a0[n], a1[n]), n
+        else:
+            nmat += 1
+            e = rel(a1[n].double() - a0[n].double(), -lr * wd * b0[n].double())
+            worst = max(worst, e)
+            assert e < 1e-3, (n, e)
+    print(f'wd step: {nmat} decayed, {nvec} undecayed parameters, worst relative error of the decay {worst:.3e}')
+    assert nmat > 0 and nvec > 0
+
+
 def test_state_dict_after_deferred_adam_is_current(setup):
     """CTCLIP.state_dict right after a step whose text Adam was deferred: copies of the
     returned tensors queued on the caller's stream -- what torch.save does -- hold the updated
