@@ -1118,6 +1118,105 @@ __device__ __forceinline__ void epilogue_geglu_bwd(const P& p, f32x4 (&acc)[8][4
   }
 }
 
+// The same epilogue with row-contiguous global accesses (EP 14, CTCLIP_GEGLU_BWD_RELAY, default
+// on).  Above, a lane of the transposed layout owns one row (lane & 15), so every 16-B load of h and
+// store of dh touches 16 rows x 64 B: the access shape store_blk_bf16_lds was written for.  Here a
+// wave's 64 g-columns are taken as what they are in memory, 256 contiguous bytes of an h / dh row
+// ([x | gate] of 32-groups t0 and t0 + 1): a 16-row block is read with 16 lanes per row, 4 whole
+// rows per instruction, staged in the wave's 4 KB LDS strip, read back in the transposed layout,
+// overwritten in place with dh and stored row-major again.  Element for element the arithmetic is
+// that of epilogue_geglu_bwd (dg rounded to bf16, the same multiplies in the same order).
+// Strip image: row r (of 16) at r * 256 B, its 16-B chunk c at chunk slot c ^ r.  The row-major
+// side touches the 16 slots of a row per 16 lanes, the transposed side (rows 0..15 at one logical
+// chunk) 16 different slots: both conflict-free for the b128 lane groups (MI355X_MICROARCH.md, LDS).
+// Wave-private scratch: LDS order within the wave is program order, no barrier.  The strip lies
+// above both 64 KB buffers (with pre1 the next tile's K-step 1 is landing in O's A1 / B1 halves).
+#ifndef GEGLU_BWD_ROWS_LA
+#define GEGLU_BWD_ROWS_LA 1
+#endif
+constexpr int GB_STRIP = 16 * 256;                       // one 16-row block of a wave: 4 KB
+constexpr int SMEM_GB = 2 * p8::TILEB + 8 * GB_STRIP;    // E + O + 8 strips = 160 KB
+__device__ __forceinline__ void epilogue_geglu_bwd_rows(const P& p, f32x4 (&acc)[8][4], int wr, int wc, int lane,
+                                                        int64_t m0, int64_t n0, int bidx, char* scr) {
+  const int64_t wrow0 = m0 + wr * 128, wcol0 = n0 + wc * 64, t0 = wcol0 >> 5;
+  if (wcol0 >= p.N) return;   // wave-uniform: the waves of the last column tile past N
+  // the strip offsets below depend on the lane only; opaque here, so they are recomputed per tile
+  // (a few VALU ops) instead of being hoisted out of the tile loop and held across the MFMA loop
+  // (36 spilled VGPRs, 8 scratch accesses per K-step pair, without this)
+  asm volatile("" : "+v"(lane));
+  const int m = lane & 15, g = lane >> 4;
+  // global side: lane = row rr of a 4-row group, 16-B chunk pc of the 256-B segment (chunks 0-7
+  // are 32-group t0, 8-15 group t0 + 1, which may lie past N)
+  const int rr = lane >> 4, pc = lane & 15;
+  const bool cok = (t0 + (pc >> 3)) * 32 < p.N;
+  const u16* hb = (const u16*)p.R + bidx * p.sR + t0 * 64 + pc * 8;
+  u16* db = (u16*)p.C + bidx * p.sC + t0 * 64 + pc * 8;
+  // transposed side: this lane's 8 g-columns are chunk co / 8 of the group's x part, + 4 of its gate
+  const int cx = pair_coff(g) >> 3;
+  // row blocks of h loads in flight: a block's registers are free as soon as it is staged, so the
+  // next load is issued right after the staging writes, ahead of the math
+  constexpr int LA = GEGLU_BWD_ROWS_LA;
+  u32x4 hr[LA][4];
+  auto load = [&](int i, int b) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t gm = wrow0 + i * 16 + q * 4 + rr;
+      hr[b][q] = (gm < p.M && cok) ? *(const u32x4*)(hb + gm * p.ldr) : make_uint4(0, 0, 0, 0);
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < LA; ++i) load(i, i);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int b = i % LA;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = q * 4 + rr;
+      *(u32x4*)(scr + r * 256 + ((pc ^ r) << 4)) = hr[b][q];
+    }
+    if (i + LA < 8) load(i + LA, b);
+#pragma unroll
+    for (int jp = 0; jp < 2; ++jp) {
+      char* sx = scr + m * 256 + (((jp * 8 + cx) ^ m) << 4);
+      char* sg = scr + m * 256 + (((jp * 8 + 4 + cx) ^ m) << 4);
+      const u32x4 hx = *(const u32x4*)sx, hg = *(const u32x4*)sg;
+      float v0[4], v1[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { v0[r] = acc[i][2 * jp][r] * p.alpha; v1[r] = acc[i][2 * jp + 1][r] * p.alpha; }
+      float d[8], x[8], gt[8], ox[8], og[8];
+      unpack8(pair_swap(v0, v1), d);
+      if (p.h16) {   // h from the fp16 forward (wave-uniform): the derivative form, two multiplies
+        unpack8h(hx, x);    // gelu(gate)
+        unpack8h(hg, gt);   // x gelu'(gate)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          ox[k] = d[k] * x[k];
+          og[k] = d[k] * gt[k];
+        }
+      } else {
+        unpack8(hx, x);
+        unpack8(hg, gt);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          float ge, dge;
+          gelu_erf_and_grad(gt[k], ge, dge);
+          ox[k] = d[k] * ge;
+          og[k] = d[k] * x[k] * dge;
+        }
+      }
+      *(u32x4*)sx = pack8(ox);
+      *(u32x4*)sg = pack8(og);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = q * 4 + rr;
+      const int64_t gm = wrow0 + i * 16 + r;
+      const u32x4 dv = *(const u32x4*)(scr + r * 256 + ((pc ^ r) << 4));
+      if (gm < p.M && cok) st16(db + gm * p.ldc, dv);
+    }
+  }
+}
+
 // ============================================================================================
 // LayerNorm fused into the epilogue of an N = 512 GEMM (ctclip_gemm_ln; the 3D-ViT's d = 512
 // rows).  A row's 512 columns are two 256-column tiles.  In the persistent walk tile_at hands the
@@ -1599,14 +1698,14 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
   // halves get the epilogue's duration to land instead of the three MFMA phases of K-step 0 (the
   // first two K-steps of a tile ran at ~3x the steady-state time, r02 stamps).  Older loads only
   // complete earlier, so the vmcnt(4) waits of the loop stay exact.
-  // Enabled for the VQ argmax GEMM (EP 3), the GEGLU backward (EP 4) and the NN dX GEMMs (EP 0 with
+  // Enabled for the VQ argmax GEMM (EP 3), the GEGLU backward (EP 4 / 14) and the NN dX GEMMs (EP 0 with
   // an N-contiguous B): 1.098 -> 1.013, 0.446 -> 0.436 and 0.313 -> 0.304 ms against the previous
   // build (profiles/r04r_gemm_pre1_ab.log).  Most of the VQ gain is the compiled code rather than
   // the prefetch (spills 18 -> 14; with p.pre1 = 0 the same build runs 1.02 ms, r04s_gemm_pre1_ab.log);
   // end to end within noise (r04s_pre1_ab_bench.log).  Skipping the re-issue costs the NT plain /
   // GEGLU / l2norm kernels 4-18 spilled VGPRs (FF1 +3 %, Q / KV +7 %), and re-issuing instead
   // gains nothing, so those keep the in-loop staging.
-  constexpr bool PRE_OK = TR && (EP == 3 || EP == 4 || (EP == 0 && !BKC));
+  constexpr bool PRE_OK = TR && (EP == 3 || EP == 4 || EP == 14 || (EP == 0 && !BKC));
   bool pre = false;
   while (true) {
     const int nk = T.nk;
@@ -1668,6 +1767,8 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
       epilogue_t<2, EP == 12, H16, X3>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
     } else if constexpr (EP == 4) {
       epilogue_geglu_bwd(p, acc, wr, wc, lane, T.m0, T.n0, T.bidx);
+    } else if constexpr (EP == 14) {
+      epilogue_geglu_bwd_rows(p, acc, wr, wc, lane, T.m0, T.n0, T.bidx, smem + 2 * TILEB + wu * GB_STRIP);
     } else if constexpr (EP == 0 || EP == 10) {
       epilogue_t<0, EP == 10>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
     } else if constexpr (EP == 3) {
@@ -1706,7 +1807,7 @@ static int g_grid_cap = 0;
 
 template <bool AK, bool BKC, int EP, bool H16 = false, bool X3 = false>
 int launch8(const P& p, int batch, hipStream_t st) {
-  constexpr int smem = EP == -6 || EP == -7 ? SMEM_LN : p8::SMEM_P;
+  constexpr int smem = EP == -6 || EP == -7 ? SMEM_LN : EP == 14 ? SMEM_GB : p8::SMEM_P;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)gemm8p_kernel<AK, BKC, EP, H16, X3>,
@@ -1778,10 +1879,17 @@ int tile_rows() { return variant() == 2 ? 2 : 1; }
 // epilogue kind, one kernel instantiation each (so the accumulator registers never share a
 // kernel with another epilogue's live ranges): -1 = LDS-staged rows (f32 / residual / argmax /
 // split-K slabs), 0 = transposed bf16, 2 = transposed GEGLU, 4 = transposed GEGLU backward,
-// 10 / 12 = 0 / 2 with their bf16 stores re-laid through LDS (store_blk_bf16_lds)
+// 10 / 12 = 0 / 2 with their bf16 stores re-laid through LDS (store_blk_bf16_lds), 14 = 4 with its h
+// loads and dh stores row-contiguous through LDS (epilogue_geglu_bwd_rows)
 template <bool AK, bool BKC>
 int launch8_ep(const P& p, int batch, hipStream_t st) {
-  if (p.act == 4) return launch8<AK, BKC, 4>(p, batch, st);
+  if (p.act == 4) {
+    // 14: h loads and dh stores row-contiguous through a wave-private LDS strip; CTCLIP_GEGLU_BWD_RELAY=0:
+    // the lane-per-row epilogue (A/B)
+    static int gb_rows = -1;
+    if (gb_rows < 0) { const char* e = getenv("CTCLIP_GEGLU_BWD_RELAY"); gb_rows = e ? atoi(e) != 0 : 1; }
+    return gb_rows ? launch8<AK, BKC, 14>(p, batch, st) : launch8<AK, BKC, 4>(p, batch, st);
+  }
   if (p.act == 5) return launch8<AK, BKC, 6>(p, batch, st);
   // CTCLIP_GEMM_TR_F32=1 (A/B): f32 / residual outputs through the transposed (LDS-free) epilogue too
   static int tr_f32 = -1;

@@ -1,5 +1,5 @@
 """Run one GEMM shape of the step repeatedly (for rocprofv3 counter passes).
-usage: python tools/gemm_one.py {ff1,ff1h16,ff1plain,ff2,dxnn,dwtn,dx1408,geglubwd,dwq} [reps]
+usage: python tools/gemm_one.py {ff1,ff1h16,ff1plain,ff2,dxnn,dwtn,dx1408,geglubwd,geglubwd16,dwq} [reps]
 (ff1h16: the step's default FF1, fp16 operands and h, GEGLU epilogue)"""
 import os
 import sys
@@ -23,6 +23,7 @@ def main():
     res = torch.randn(M, 512, device='cuda')
     dh = r(M, 2816)
     x512h, w1h = x512.half(), w1.half()
+    dh16 = dh.half() if which == 'geglubwd16' else None   # h as the step's fp16 FF1 stores it
     fn = {
         'ff1': lambda: K.linear(x512, w1, act=K.ACT_GEGLU, out2=g),
         'ff1h16': lambda: K.linear(x512h, w1h, act=K.ACT_GEGLU, out2=g, out_dtype=K.F16),
@@ -32,6 +33,7 @@ def main():
         'dwtn': lambda: K.matmul_tn(dh, x512),
         'dx1408': lambda: K.matmul_nn(x512, w2),
         'geglubwd': lambda: K.matmul_nn_geglu_bwd(x512, w2, dh),
+        'geglubwd16': lambda: K.matmul_nn_geglu_bwd(x512, w2, dh16),
         'dwq': lambda: K.matmul_tn(x512[:, :256], x512),
     }[which]
     for _ in range(reps):
