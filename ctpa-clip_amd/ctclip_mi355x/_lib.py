@@ -126,6 +126,16 @@ class ResampleArgs(ctypes.Structure):
     ]
 
 
+class EvalVolumeArgs(ctypes.Structure):
+    """ctclip_eval_volume_args (include/ctclip_hip.h): the evaluation loader."""
+    _fields_ = [
+        ('src', c_vp), ('src_dtype', c_i32),
+        ('D', c_i64), ('H', c_i64), ('W', c_i64), ('sd', c_i64), ('sh', c_i64), ('sw', c_i64),
+        ('Do', c_i64), ('Ho', c_i64), ('Wo', c_i64), ('od', c_i64), ('oh', c_i64), ('ow', c_i64),
+        ('fill', c_f32),
+    ]
+
+
 class ClipLossExArgs(ctypes.Structure):
     """ctclip_clip_loss_ex_args (include/ctclip_hip.h): the general contrastive loss."""
     _fields_ = [
@@ -256,6 +266,8 @@ _SIGS = {
     'ctclip_clip_scores': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp],
     'ctclip_zero_shot': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],
+    'ctclip_eval_volume': [ctypes.POINTER(EvalVolumeArgs), c_vp, c_vp],
+    'ctclip_auroc_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
     'ctclip_sgemm': [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
                      c_i32, c_f32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp],
     'ctclip_embed_fwd': [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],

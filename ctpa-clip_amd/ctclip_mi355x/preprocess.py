@@ -18,7 +18,7 @@ import ctypes
 
 import torch
 
-from ._lib import call, ptr, stream_ptr, ResampleArgs
+from ._lib import call, ptr, stream_ptr, ResampleArgs, EvalVolumeArgs
 
 TARGET_SPACING = (1.5, 0.75, 0.75)      # (z, x, y): data.py:134-136, preprocess_train.py:89-91
 TARGET_SHAPE = (480, 480, 240)          # (h, w, d): data.py:155
@@ -85,5 +85,41 @@ def preprocess_offline(img, slope, intercept, xy_spacing, z_spacing):
     return out
 
 
-__all__ = ['ct_volume_to_tensor', 'preprocess_offline', 'resized_shape', 'crop_pad', 'TARGET_SHAPE',
-           'TARGET_SPACING']
+def eval_volume_to_tensor(scan, target_shape=TARGET_SHAPE, out=None):
+    """The evaluation / inference loader, ``ct_clip/data_inference.py:78-122`` (nii_img_to_tensor):
+    ``arr_0`` as stored (device tensor, f32 or f64, axes (a0, a1, a2) read as (h, w, d) =
+    (a1, a2, a0), data_inference.py:80) -> x * 1000, clip to [-1000, 200], (v + 400) / 600, centre
+    crop / pad (value -1) to ``target_shape`` -> (1, D, H, W) f32.  No resampling, and a
+    normalisation of its own: not the training loader's (``ct_volume_to_tensor``).
+
+    ``out``: a contiguous (1, D, H, W) f32 device tensor to write into, e.g. a row ``batch[i]`` of
+    an (N, 1, D, H, W) batch; it is returned."""
+    if scan.ndim != 3:
+        raise ValueError(f'preprocess: expected a 3-D scan, got {tuple(scan.shape)}')
+    if scan.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f'preprocess: unsupported scan dtype {scan.dtype} (the evaluation loader takes the '
+                         'normalised float32 / float64 scans the reference stores)')
+    if not scan.is_cuda:
+        raise ValueError('preprocess: the scan must be a device tensor')
+    h, w, d = 1, 2, 0                                   # np.transpose(img_data, (1, 2, 0)), :80
+    th, tw, td = target_shape
+    (hs, hp), (ws, wp), (ds, dp) = crop_pad(scan.shape[h], th), crop_pad(scan.shape[w], tw), crop_pad(scan.shape[d], td)
+    if out is None:
+        out = torch.empty(1, td, th, tw, device=scan.device, dtype=torch.float32)
+    elif (tuple(out.shape) != (1, td, th, tw) or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != scan.device):
+        raise ValueError(f'preprocess: out must be a contiguous float32 {(1, td, th, tw)} tensor on {scan.device}, '
+                         f'got {out.dtype} {tuple(out.shape)} on {out.device}')
+    a = EvalVolumeArgs()
+    a.src, a.src_dtype = ptr(scan), _DT[scan.dtype]
+    a.D, a.H, a.W = scan.shape[d], scan.shape[h], scan.shape[w]
+    a.sd, a.sh, a.sw = scan.stride(d), scan.stride(h), scan.stride(w)
+    a.Do, a.Ho, a.Wo = td, th, tw
+    a.od, a.oh, a.ow = dp - ds, hp - hs, wp - ws
+    a.fill = -1.0
+    call('ctclip_eval_volume', ctypes.byref(a), ptr(out), stream_ptr())
+    return out
+
+
+__all__ = ['ct_volume_to_tensor', 'eval_volume_to_tensor', 'preprocess_offline', 'resized_shape', 'crop_pad',
+           'TARGET_SHAPE', 'TARGET_SPACING']

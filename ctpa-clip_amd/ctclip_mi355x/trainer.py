@@ -121,6 +121,13 @@ class NonFiniteStepError(StepGuardError):
     parameter; here no rank applied the step."""
 
 
+class EvalGuardError(StepGuardError):
+    """A validation pass (``CTClipTrainer.validate``) was flagged on the device: one of its eval
+    forwards set status bits (``bits``; e.g. a non-finite validation volume), so its scores are not
+    to be trusted.  Nothing was trained by it, and the sticky status word was put back to what it was
+    before the pass: no later ``train_step`` is skipped or blamed for it."""
+
+
 _STATUS_NAMES = ((1, 'LayerNorm exchange timeout'), (2, 'fp16 range (saturated / non-finite fp16 operand)'),
                  (4, 'non-finite gradient norm'), (8, 'non-finite VQ token'))
 
@@ -356,6 +363,63 @@ class CTClipTrainer:
         streams.join_text(self.device)
         streams.join_aux(self.device)
         self.check()
+
+    def validate(self, volumes, labels, classifier=None, n_boot=0, batch_size=8):
+        """The reference trainer's validation pass between steps (CTCLIPTrainer.py:356-454): score
+        ``volumes`` zero-shot with ``classifier`` (a ``zero_shot.ZeroShotClassifier`` of this model
+        with its prompts set -- the reference's are ``VALIDATION_PATHOLOGIES`` with
+        ``VALIDATION_TEMPLATE``; None: the one passed last time) and return
+        ``evaluate.ZeroShotEvaluator.evaluate``'s dict (probs, auroc, ci, f1_micro, flat_accuracy).
+
+        ``flush()`` runs first, so every queued step is applied and verified (a StepGuardError raised
+        here belongs to a training step).  The prompts are encoded again with the current weights,
+        the forwards run in eval mode under ``no_grad`` (no codebook EMA), and the training mode is
+        restored afterwards.
+
+        The pass owns its status bits: the sticky per-device status word is saved and cleared before
+        the eval forwards, read after them and put back as it was found.  If the forwards set any
+        bit (e.g. a non-finite volume), ``EvalGuardError`` names them; the next ``train_step`` is
+        neither skipped nor blamed.
+
+        With world > 1 EVERY rank must call ``validate`` at the same step: ``flush()`` runs a pending
+        codebook EMA, whose counts are all-reduced, on all ranks together.  (The reference validates on
+        the main process only; here the other ranks may pass an empty result away, but must call.)
+        Should an EMA still be pending when the eval forward is about to start, this raises instead of
+        letting the forward issue that collective on one rank."""
+        from .evaluate import ZeroShotEvaluator
+        if classifier is None:
+            classifier = getattr(self, '_val_classifier', None)
+            if classifier is None:
+                raise ValueError('CTClipTrainer.validate: pass classifier= (a ZeroShotClassifier with prompts set)')
+        if classifier.model is not self.model:
+            raise ValueError('CTClipTrainer.validate: the classifier scores another model')
+        self._val_classifier = classifier
+        self.flush()
+        vqs = getattr(self.model, '_vq_state', lambda: None)()
+        if vqs is not None and vqs.pending_ema is not None:
+            raise RuntimeError('CTClipTrainer.validate: a codebook EMA update is still pending after flush(); the eval '
+                               'forward would queue it (a collective with world > 1) -- refusing to')
+        word = K.status_word(self.device) if self._guard else None
+        snap = word.clone() if word is not None else None
+        was = self.model.training
+        self.model.eval()
+        try:
+            if word is not None:
+                word.zero_()
+            with torch.no_grad():
+                classifier.refresh()
+                res = ZeroShotEvaluator(classifier).evaluate(volumes, labels, n_boot=n_boot, batch_size=batch_size)
+            bits = int(word.item()) if word is not None else 0      # synchronises: the forwards are done
+        finally:
+            if word is not None:
+                word.copy_(snap)
+            self.model.train(was)
+        if bits:
+            raise EvalGuardError(
+                f'validation after step {self.steps} was flagged on the device, status {bits} '
+                f'({describe_status(bits)}): its scores are not reported.  The status word was restored to '
+                f'{int(snap.item())}, training is unaffected', bits=bits)
+        return res
 
     def check(self):
         """Wait for every queued step-status copy and raise LayerNormExchangeError if a step's

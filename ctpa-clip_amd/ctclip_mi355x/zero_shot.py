@@ -28,11 +28,21 @@ PATHOLOGIES = ('Medical material', 'Arterial wall calcification', 'Cardiomegaly'
                'Interlobular septal thickening')
 
 
-def prompts(pathologies=PATHOLOGIES):
-    """The prompt pairs of ``ctclip_inference.py:306``, flattened: rows 2j / 2j+1."""
+# the trainer's validation pass scores another list with another prompt pair
+# (ct_clip/CTCLIPTrainer.py:378-408): entry 11 is 'Pulmonary fibrotic sequela' there
+VALIDATION_PATHOLOGIES = PATHOLOGIES[:11] + ('Pulmonary fibrotic sequela',) + PATHOLOGIES[12:]
+INFERENCE_TEMPLATE = ('{} is present.', '{} is not present.')
+VALIDATION_TEMPLATE = ('There is {}.', 'There is no {}.')
+
+
+def prompts(pathologies=PATHOLOGIES, template=INFERENCE_TEMPLATE):
+    """The prompt pairs of ``ctclip_inference.py:306``, flattened: rows 2j / 2j+1.  ``template``:
+    the (positive, negative) pair of format strings; ``VALIDATION_TEMPLATE`` gives the trainer's
+    validation prompts (``CTCLIPTrainer.py:405-408``)."""
+    pos, neg = template
     out = []
     for p in pathologies:
-        out += [f'{p} is present.', f'{p} is not present.']
+        out += [pos.format(p), neg.format(p)]
     return out
 
 
@@ -43,15 +53,16 @@ class ZeroShotClassifier:
     ``padding='max_length', truncation=True, max_length=512``) or pre-tokenised ``text`` (any
     object with ``.input_ids`` / ``.attention_mask`` of 2P rows) via ``set_prompts``."""
 
-    def __init__(self, model, pathologies=PATHOLOGIES, tokenizer=None, max_length=512):
+    def __init__(self, model, pathologies=PATHOLOGIES, tokenizer=None, max_length=512, template=INFERENCE_TEMPLATE):
         self.model = model
         self.pathologies = tuple(pathologies)
         self.max_length = max_length
+        self.template = tuple(template)
         self._t_raw = None
         if tokenizer is not None:
             dev = next(model.parameters()).device
-            self.set_prompts(tokenizer(prompts(self.pathologies), return_tensors='pt', padding='max_length',
-                                       truncation=True, max_length=max_length).to(dev))
+            self.set_prompts(tokenizer(prompts(self.pathologies, self.template), return_tensors='pt',
+                                       padding='max_length', truncation=True, max_length=max_length).to(dev))
 
     def set_prompts(self, text):
         ids = text.input_ids
@@ -59,10 +70,18 @@ class ZeroShotClassifier:
             raise ValueError(f'expected {2 * len(self.pathologies)} prompt rows (a present / not present pair '
                              f'per pathology), got {ids.shape[0]}')
         m = self.model
+        self._text = text
         with torch.no_grad(), _eval(m):
             enc = m.text_transformer(ids, attention_mask=text.attention_mask)[0]
             self._t_raw = Fn.TextProjFn.apply(enc[:, 0, :].contiguous(), m.to_text_latent.weight)
         return self
+
+    def refresh(self):
+        """Encode the prompts again with the model's current weights (the cached latents are those
+        of the weights at ``set_prompts`` time; ``CTClipTrainer.validate`` calls this)."""
+        if self._t_raw is None:
+            raise RuntimeError('ZeroShotClassifier: no prompts (pass tokenizer= or call set_prompts)')
+        return self.set_prompts(self._text)
 
     def image_latents(self, volumes):
         """Raw projected image latents [N, Dl] (image tower + VQ + pool + to_visual_latent)."""

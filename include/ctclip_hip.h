@@ -735,6 +735,39 @@ typedef struct {
 } ctclip_resample_args;
 int ctclip_resample_volume(const ctclip_resample_args* a, float* out, void* stream);
 
+/* ---------------------------------------------------------------- evaluation loader
+ * ct_clip/data_inference.py:78-122 (CTReportDatasetinfer.nii_img_to_tensor), the loader of the
+ * validation / inference volumes: v = x * 1000 -> clip(-1000, 200) -> (v + 400) / 600 -> centre
+ * crop / pad (fill) -> (D, H, W) f32; no resampling.  f32 sources compute in f32, f64 sources in
+ * f64 rounded to f32 once (numpy's types), each operation rounded on its own.  src_dtype:
+ * CTCLIP_F32 or CTCLIP_F64 (CT_EINVAL otherwise).  The source is read through (d, h, w) element
+ * strides (the stored (a0, a1, a2) scan is (h, w, d) = (a1, a2, a0): sd = a1*a2, sh = a2, sw = 1,
+ * contiguous along w like the output).  Output voxel (d, h, w) takes source voxel
+ * (d-od, h-oh, w-ow), or `fill` outside [0,D) x [0,H) x [0,W); the host computes the offsets with
+ * the reference's floor divisions (ctclip_mi355x/preprocess.py).  16-byte loads / stores where the
+ * addresses allow, scalar ones otherwise: any element-aligned src / out is accepted. */
+typedef struct {
+  const void* src; int32_t src_dtype;
+  int64_t D, H, W;          /* source extents in the (d, h, w) view */
+  int64_t sd, sh, sw;       /* source strides, elements, >= 0 */
+  int64_t Do, Ho, Wo;       /* output extents, Do < 65536 */
+  int64_t od, oh, ow;       /* output index - source index (crop / pad placement) */
+  float fill;
+} ctclip_eval_volume_args;
+int ctclip_eval_volume(const ctclip_eval_volume_args* a, float* out, void* stream);
+
+/* ---------------------------------------------------------------- evaluation metrics
+ * AUROC of S bootstrap resamples x P labels (ct_clip/evaluate.py:160-207 per resample of
+ * evaluate.py:305-337): scores [N][P] f32, labels [N][P] uint8 (non-zero = positive), order [P][N]
+ * = per label the rows sorted by ascending score (ties in any order), resample [S][N] = the rows
+ * each resample draws (row 0 may be the identity: the point estimate) -> out [S][P] f64, the
+ * tie-aware Mann-Whitney count sum_g pos_g (2 neg_below_g + neg_g) over runs g of bit-equal
+ * scores, accumulated in 64-bit integers and divided once by 2 Pos Neg (NaN when Pos Neg = 0, as
+ * roc_curve + auc give for a one-class sample).  Integer-exact: independent of launch geometry.
+ * 1 <= N <= 8192 (LDS), P >= 1, S >= 1: CT_ESHAPE otherwise. */
+int ctclip_auroc_boot(const float* scores, const uint8_t* labels, const int32_t* order, const int32_t* resample,
+                      int32_t N, int32_t P, int32_t S, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
