@@ -156,6 +156,18 @@ class BertModel(nn.Module):
         ids = {id(p) for p in first}
         return first + [p for p in self.parameters() if id(p) not in ids]
 
+    def dropout_state(self):
+        """The forward-call counter the dropout seeds are hashed from (``_forward``): with
+        ``torch.initial_seed()`` it is the whole state of the dropout stream (checkpoints save it)."""
+        return getattr(self, '_drop_calls', 0)
+
+    def set_dropout_state(self, n):
+        """Continue the dropout stream after forward call ``n`` (``dropout_state`` of a saved run)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f'BertModel.set_dropout_state: a call count, got {n}')
+        self._drop_calls = n
+
     def forward(self, input_ids, attention_mask=None, join=True, ready=None, **_):
         """Runs on the text stream (streams.py) when there is one, ordered after ``ready`` (an event
         of the calling stream; default: everything queued on it so far) and after the previous

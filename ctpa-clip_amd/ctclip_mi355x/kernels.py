@@ -1341,6 +1341,13 @@ def weights_epoch():
     return _WEIGHTS_EPOCH[0]
 
 
+def advance_weights_epoch():
+    """Start a new weights epoch without an Adam launch: for a writer that replaced parameters
+    wholesale (a checkpoint load), so every epoch-keyed cache of derived weights is rebuilt."""
+    _WEIGHTS_EPOCH[0] += 1
+    return _WEIGHTS_EPOCH[0]
+
+
 def adam(p, g, m, v, *, lr, b1, b2, eps, wd, step, coef=None, p_bf16=None, p_bf16_lo=None, zero_grad=False,
          skip=None):
     """skip: optional device int32[1] guard word; when nonzero the launch changes nothing."""

@@ -14,6 +14,7 @@ import os
 import torch
 
 
+from . import checkpoint
 from . import dist_sync
 from . import streams
 from . import kernels as K
@@ -363,6 +364,38 @@ class CTClipTrainer:
         streams.join_text(self.device)
         streams.join_aux(self.device)
         self.check()
+
+    def save(self, path):
+        """Write the whole training state to ``path`` (CTCLIPTrainer.py:289-298; checkpoint.py has the
+        layout): model ``state_dict``, Adam moments and step count keyed by parameter name, the
+        hyper-parameters and the RNG state (seed, BERT's dropout counter, torch's generators).
+
+        EVERY rank calls it at the same step: ``flush()`` runs first (a deferred text Adam, a pending
+        codebook EMA -- a collective with world > 1 -- and the step status check, which raises
+        StepGuardError before anything is written), rank 0 alone writes, and all ranks meet at a
+        barrier.  The write is atomic: ``path + '.tmp'`` then ``os.replace``; a failed write leaves an
+        existing ``path`` as it was."""
+        checkpoint.save(self, path)
+
+    def load(self, path, strict=True, restore_rng=True):
+        """Continue from ``save``'s package: a run stopped there and resumed here computes the bits of
+        one that never stopped, whatever ``wd`` / ``overlap_grad_sync`` arena order either side uses
+        (DESIGN.md §18 lists what must be equal on both sides).  EVERY rank calls it and reads the
+        file.  ``flush()`` runs first; the weights land in the arena, the bf16 shadows are re-cast,
+        the weights epoch advances (derived-weight caches), moments, step count and -- unless
+        ``restore_rng=False`` -- the RNG state are restored, the gradient arena is cleared.
+
+        Also read: a bare model ``state_dict`` (the reference's periodic ``CTClip.{steps}.pt``) and a
+        ``{model, optim}`` package; a uniform ``module.`` key prefix is stripped.  Weights alone leave
+        moments and step count as they are.  An ``optim`` that is not name-keyed (the reference's
+        positional ``torch.optim.Adam.state_dict()``) raises ``checkpoint.ForeignOptimizerError``
+        after the model was loaded.  A trainable parameter without moments in the file, or with
+        another shape, raises KeyError / ValueError naming it before anything is changed.
+
+        The hyper-parameters stay the constructor's; returns ``{missing_keys, unexpected_keys,
+        hyper_mismatch, step}`` (``hyper_mismatch``: saved and current wd / betas / eps that differ,
+        also warned)."""
+        return checkpoint.load(self, path, strict=strict, restore_rng=restore_rng)
 
     def validate(self, volumes, labels, classifier=None, n_boot=0, batch_size=8):
         """The reference trainer's validation pass between steps (CTCLIPTrainer.py:356-454): score
