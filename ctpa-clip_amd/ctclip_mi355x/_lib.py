@@ -149,7 +149,12 @@ class ClipLossExArgs(ctypes.Structure):
     ]
 
 
-# name -> argtypes (restype is always int32)
+class ClipLossTiledArgs(ctypes.Structure):
+    """ctclip_clip_loss_tiled_args (include/ctclip_hip.h): the tiled MFMA contrastive loss."""
+    _fields_ = ClipLossExArgs._fields_[:-1] + [('ws_bytes', c_i64), ('grad_row0', c_i32), ('grad_rows', c_i32)]
+
+
+# name -> argtypes (restype is int32 unless _RESTYPES names another)
 _SIGS = {
     'ctclip_version': [],
     'ctclip_device_arch': [ctypes.c_char_p, c_i32],
@@ -263,6 +268,8 @@ _SIGS = {
     'ctclip_clip_loss': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'ctclip_clip_loss_ex': [ctypes.POINTER(ClipLossExArgs), c_vp],
     'ctclip_clip_loss_ex_ws_floats': [ctypes.POINTER(ClipLossExArgs)],
+    'ctclip_clip_loss_tiled': [ctypes.POINTER(ClipLossTiledArgs), c_vp],
+    'ctclip_clip_loss_tiled_ws_bytes': [ctypes.POINTER(ClipLossTiledArgs)],
     'ctclip_clip_scores': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp],
     'ctclip_zero_shot': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],
@@ -277,6 +284,7 @@ _SIGS = {
     'ctclip_adam': [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_i32,
                     c_vp, c_vp],
 }
+_RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64}
 
 
 def register(name, argtypes):
@@ -284,7 +292,7 @@ def register(name, argtypes):
     if _LIB is not None:
         fn = getattr(_LIB, name)
         fn.argtypes = argtypes
-        fn.restype = c_i32
+        fn.restype = _RESTYPES.get(name, c_i32)
 
 
 def lib():
@@ -310,7 +318,7 @@ def lib():
                 continue
             fn = getattr(_LIB, name)
             fn.argtypes = argtypes
-            fn.restype = c_i32
+            fn.restype = _RESTYPES.get(name, c_i32)
     return _LIB
 
 

@@ -10,6 +10,7 @@ encoders: decoupled_contrastive_learning (ct_clip.py:865-867), extra_latent_proj
 (``aug_image=``, :663-675,:882-899).  The plain configuration runs ``functional.ClipLossFn`` on the
 one-workgroup kernel as before; any of the three options switches the loss to
 ``functional.ClipLossExFn`` (one workgroup per view pair + a fixed-order reduction).
+Above 128 gathered rows both Functions take the tiled MFMA loss (``functional.set_loss_tiled``).
 ``aug_text`` (the reference itself cannot run it: it calls ``.shape`` on a BatchEncoding) and
 everything else raises.
 """

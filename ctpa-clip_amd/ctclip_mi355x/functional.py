@@ -1218,6 +1218,33 @@ class TextProjFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- loss
+# Which contrastive-loss implementation the autograd Functions and custom ops take for a gathered batch
+# of Bg rows: the one-workgroup kernels (kernels.clip_loss / clip_loss_ex, Bg <= 128) or the tiled MFMA
+# kernels (kernels.clip_loss_tiled, Bg <= 8192).  'auto': tiled only where the others cannot run.
+LOSS_TILED_MODES = ('auto', 'always', 'never')
+LOSS_ONE_WORKGROUP_MAX = 128
+_LOSS_TILED = {'mode': 'auto'}
+
+
+def loss_tiled_mode():
+    return _LOSS_TILED['mode']
+
+
+def set_loss_tiled(mode):
+    """Select the contrastive-loss dispatch: 'auto' (tiled iff Bg > 128), 'always' or 'never';
+    returns the previous mode."""
+    if mode not in LOSS_TILED_MODES:
+        raise ValueError(f'set_loss_tiled: mode {mode!r} is not one of {LOSS_TILED_MODES}')
+    old = _LOSS_TILED['mode']
+    _LOSS_TILED['mode'] = mode
+    return old
+
+
+def loss_uses_tiled(Bg):
+    """Whether a gathered batch of Bg rows takes the tiled loss under the current mode."""
+    mode = _LOSS_TILED['mode']
+    return mode == 'always' or (mode == 'auto' and int(Bg) > LOSS_ONE_WORKGROUP_MAX)
+
 
 class ClipLossFn(torch.autograd.Function):
     """Symmetric InfoNCE (ct_clip/ct_clip.py:845-901).  Under torch.distributed the raw latents
@@ -1230,8 +1257,15 @@ class ClipLossFn(torch.autograd.Function):
         tg, ig = dist_sync.gather_latents(t_raw, i_raw, t_gather)
         # impl: the fused HIP loss (default); tests substitute a CPU restatement to exercise
         # the exchange logic under gloo
-        loss, dt, di, dlt = (impl or K.clip_loss)(tg, ig, log_temp.reshape(1).contiguous())[:4]
-        ctx.save_for_backward(dist_sync.local_rows(dt, B), dist_sync.local_rows(di, B), dlt)
+        if impl is None and loss_uses_tiled(tg.shape[0]):
+            # the tiled kernels produce this rank's rows only (one-view stacks)
+            loss, dt, di, _, _, dlt, _ = K.clip_loss_tiled(tg.unsqueeze(0), ig.unsqueeze(0),
+                                                           log_temp.reshape(1).contiguous(),
+                                                           rows=(dist_sync.world_rank()[1] * B, B))
+            ctx.save_for_backward(dt[0], di[0], dlt)
+        else:
+            loss, dt, di, dlt = (impl or K.clip_loss)(tg, ig, log_temp.reshape(1).contiguous())[:4]
+            ctx.save_for_backward(dist_sync.local_rows(dt, B), dist_sync.local_rows(di, B), dlt)
         ctx.scale = dist_sync.replicated_grad_scale()
         return loss.reshape(())
 
@@ -1262,11 +1296,16 @@ class ClipLossExFn(torch.autograd.Function):
                                          [i_raw, i_extra] if has_x else [i_raw], t_gather)
         # impl: the fused HIP loss (default); tests substitute a CPU restatement to exercise the
         # exchange logic under gloo
-        loss, dt, di, dtx, dix, dlt = (impl or K.clip_loss_ex)(
-            tg[0], ig[0], log_temp.reshape(1).contiguous(), tg[1] if has_x else None, ig[1] if has_x else None,
-            decoupled, w_main, w_multiview)[:6]
-        saved = [dt, di] + ([dtx, dix] if has_x else [])
-        ctx.save_for_backward(dlt, *[dist_sync.local_view_rows(g, B) for g in saved])
+        args = (tg[0], ig[0], log_temp.reshape(1).contiguous(), tg[1] if has_x else None, ig[1] if has_x else None,
+                decoupled, w_main, w_multiview)
+        if impl is None and loss_uses_tiled(tg[0].shape[1]):
+            # the tiled kernels produce this rank's rows only
+            loss, dt, di, dtx, dix, dlt = K.clip_loss_tiled(*args, rows=(dist_sync.world_rank()[1] * B, B))[:6]
+            ctx.save_for_backward(dlt, dt, di, *([dtx, dix] if has_x else []))
+        else:
+            loss, dt, di, dtx, dix, dlt = (impl or K.clip_loss_ex)(*args)[:6]
+            saved = [dt, di] + ([dtx, dix] if has_x else [])
+            ctx.save_for_backward(dlt, *[dist_sync.local_view_rows(g, B) for g in saved])
         ctx.has_x = has_x
         ctx.scale = dist_sync.replicated_grad_scale()
         return loss.reshape(())

@@ -1241,6 +1241,46 @@ def clip_loss_ex(t_raw, i_raw, log_temp, t_extra=None, i_extra=None, decoupled=F
     return loss, dt, di, dtx, dix, dlt, pair
 
 
+def clip_loss_tiled(t_raw, i_raw, log_temp, t_extra=None, i_extra=None, decoupled=False, w_main=1.0, w_multiview=0.0,
+                    rows=None):
+    """``clip_loss_ex`` on the tiled MFMA kernels (ctclip_clip_loss_tiled): Bg up to 8192.  Returns the
+    same 7-tuple; with ``rows=(row0, n)`` the latent gradients cover rows [row0, row0 + n) of every view
+    only and come as [V, n, Dl] stacks (loss, pair losses and dlt stay the full global values)."""
+    if t_raw.dim() != 3 or i_raw.dim() != 3 or t_raw.shape[1:] != i_raw.shape[1:]:
+        raise ValueError(f'clip_loss_tiled: [views, Bg, Dl] stacks, got {tuple(t_raw.shape)} / {tuple(i_raw.shape)}')
+    if (t_extra is None) != (i_extra is None):
+        raise ValueError('clip_loss_tiled: the extra latents come as a pair')
+    if t_extra is not None and (t_extra.shape != t_raw.shape or i_extra.shape != i_raw.shape):
+        raise ValueError('clip_loss_tiled: the extra latents have the shapes of the main ones')
+    tens = [x if x is None else x.contiguous() for x in (t_raw, i_raw, t_extra, i_extra)]
+    if any(x is not None and x.dtype != F32 for x in tens) or log_temp.dtype != F32:
+        raise ValueError('clip_loss_tiled: f32 inputs')
+    t_raw, i_raw, t_extra, i_extra = tens
+    Vt, Bg, Dl = t_raw.shape
+    Vi = i_raw.shape[0]
+    row0, n = (0, Bg) if rows is None else (int(rows[0]), int(rows[1]))
+    if row0 < 0 or n < 1 or row0 + n > Bg:
+        raise ValueError(f'clip_loss_tiled: rows {(row0, n)} outside the {Bg} global rows')
+    dev = t_raw.device
+    loss = torch.empty(1, device=dev, dtype=F32)
+    dlt = torch.empty(1, device=dev, dtype=F32)
+    pair = torch.empty(Vt * Vi, device=dev, dtype=F32)
+    dt = torch.empty(Vt, n, Dl, device=dev, dtype=F32)
+    di = torch.empty(Vi, n, Dl, device=dev, dtype=F32)
+    dtx = torch.empty_like(dt) if t_extra is not None else None
+    dix = torch.empty_like(di) if i_extra is not None else None
+    a = _lib.ClipLossTiledArgs(t_raw=ptr(t_raw), i_raw=ptr(i_raw), t_extra=ptr(t_extra), i_extra=ptr(i_extra),
+                               log_temp=ptr(log_temp), Vt=Vt, Vi=Vi, Bg=Bg, Dl=Dl, decoupled=int(bool(decoupled)),
+                               w_main=float(w_main), w_multiview=float(w_multiview), loss=ptr(loss),
+                               pair_loss=ptr(pair), dt_raw=ptr(dt), di_raw=ptr(di), dt_extra=ptr(dtx),
+                               di_extra=ptr(dix), dlogtemp=ptr(dlt), grad_row0=row0, grad_rows=n)
+    nbytes = _lib.lib().ctclip_clip_loss_tiled_ws_bytes(_lib.ctypes.byref(a))
+    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=F32)
+    a.ws, a.ws_bytes = ptr(ws), nbytes
+    call('ctclip_clip_loss_tiled', _lib.ctypes.byref(a), stream_ptr())
+    return loss, dt, di, dtx, dix, dlt, pair
+
+
 def zero_shot(t_raw, i_raw, log_temp):
     """Raw prompt latents [2P, Dl] (pairs present / not present) x raw image latents [N, Dl] ->
     (probs [N, P], scores [N, P, 2]); ct_clip/ctclip_inference.py:305-315."""

@@ -192,6 +192,11 @@ def _clip_infonce(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor)
     _need(text_latents.dtype == image_latents.dtype == log_temp.dtype == F32, 'clip_infonce: f32 inputs')
     _need(text_latents.shape == image_latents.shape and text_latents.dim() == 2, 'clip_infonce: [B, dim_latent]')
     _need(log_temp.numel() == 1, 'clip_infonce: log_temp is a scalar')
+    from . import functional as Fn
+    if Fn.loss_uses_tiled(text_latents.shape[0]):      # the tiled MFMA loss, full rows
+        loss, dt, di, _, _, dlt, _ = K.clip_loss_tiled(text_latents.unsqueeze(0), image_latents.unsqueeze(0),
+                                                       log_temp.reshape(1).contiguous())
+        return loss.reshape(()), dt[0], di[0], dlt.reshape(log_temp.shape)
     loss, dt, di, dlt, _, _, _ = K.clip_loss(text_latents.contiguous(), image_latents.contiguous(),
                                              log_temp.reshape(1).contiguous())
     return loss.reshape(()), dt, di, dlt.reshape(log_temp.shape)
@@ -235,8 +240,10 @@ def _clip_infonce_ex(text_latents: Tensor, image_latents: Tensor, log_temp: Tens
                                  and text_extra.dtype == image_extra.dtype == F32),
           'clip_infonce_ex: the extra latents have the shapes of the main ones (f32)')
     _need(log_temp.numel() == 1, 'clip_infonce_ex: log_temp is a scalar')
-    loss, dt, di, dtx, dix, dlt, pair = K.clip_loss_ex(text_latents, image_latents, log_temp.reshape(1).contiguous(),
-                                                       text_extra, image_extra, decoupled, w_main, w_multiview)
+    from . import functional as Fn
+    impl = K.clip_loss_tiled if Fn.loss_uses_tiled(text_latents.shape[1]) else K.clip_loss_ex
+    loss, dt, di, dtx, dix, dlt, pair = impl(text_latents, image_latents, log_temp.reshape(1).contiguous(),
+                                             text_extra, image_extra, decoupled, w_main, w_multiview)
     if dtx is None:
         dtx, dix = text_latents.new_empty(0), text_latents.new_empty(0)
     return loss.reshape(()), dt, di, dtx, dix, dlt.reshape(log_temp.shape), pair

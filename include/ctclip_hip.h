@@ -658,6 +658,32 @@ typedef struct {
 } ctclip_clip_loss_ex_args;
 int ctclip_clip_loss_ex(const ctclip_clip_loss_ex_args* a, void* stream);
 int ctclip_clip_loss_ex_ws_floats(const ctclip_clip_loss_ex_args* a);
+/* The same loss for global batches the one-workgroup kernels cannot hold (csrc/loss_tiled.hip): the
+ * Bg x Bg logits and both gradient products run tiled on the f32 matrix pipe (exact f32), in separate
+ * launches -- normalise once, logits + partial sums, sums, gradients, l2norm backward -- with every
+ * cross-tile sum in a fixed order: no float atomics, bit-reproducible.  Fields as
+ * ctclip_clip_loss_ex_args; the latent gradients are produced for rows [grad_row0, grad_row0 +
+ * grad_rows) of every view only and land in [V][grad_rows][Dl] outputs (a row's bits do not depend on
+ * the range it was asked in); loss, pair_loss and dlogtemp are always the full global values.
+ * ws: ctclip_clip_loss_tiled_ws_bytes(a) bytes, 16-B aligned (0 = unsupported shape; 64-bit: exp(S) of
+ * every pair is stored).  1 <= Bg <= 8192, 1 <= Dl <= 8192, P <= 64: CT_ESHAPE otherwise; a missing
+ * pointer, half an extra pair, a short ws or a row range outside [0, Bg]: CT_EINVAL. */
+typedef struct {
+  const float* t_raw; const float* i_raw;
+  const float* t_extra; const float* i_extra;   /* optional, both or neither */
+  const float* log_temp;
+  int32_t Vt, Vi, Bg, Dl;
+  int32_t decoupled;
+  float w_main, w_multiview;
+  float* loss; float* pair_loss;
+  float* dt_raw; float* di_raw;                 /* [Vt][grad_rows][Dl], [Vi][grad_rows][Dl] */
+  float* dt_extra; float* di_extra;             /* required with the extra pair */
+  float* dlogtemp;
+  float* ws; int64_t ws_bytes;
+  int32_t grad_row0, grad_rows;
+} ctclip_clip_loss_tiled_args;
+int ctclip_clip_loss_tiled(const ctclip_clip_loss_tiled_args* a, void* stream);
+int64_t ctclip_clip_loss_tiled_ws_bytes(const ctclip_clip_loss_tiled_args* a);
 /* eval branch einsum('b d, b d -> b') * temp (ct_clip.py:805-807); with extra_latent_projection and
  * text_to_image = False the caller passes the extra latents (:806) */
 int ctclip_clip_scores(const float* t_raw, const float* i_raw, int32_t B, int32_t Dl, const float* log_temp,
