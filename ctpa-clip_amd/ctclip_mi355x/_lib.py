@@ -275,6 +275,10 @@ _SIGS = {
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],
     'ctclip_eval_volume': [ctypes.POINTER(EvalVolumeArgs), c_vp, c_vp],
     'ctclip_auroc_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
+    'ctclip_retrieval_ranks_ws_bytes': [c_i32, c_i32, c_i32],
+    'ctclip_retrieval_ranks': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
+    'ctclip_retrieval_topk_ws_bytes': [c_i32, c_i32, c_i32, c_i32],
+    'ctclip_retrieval_topk': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
     'ctclip_sgemm': [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
                      c_i32, c_f32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp],
     'ctclip_embed_fwd': [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -284,7 +288,8 @@ _SIGS = {
     'ctclip_adam': [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_i32,
                     c_vp, c_vp],
 }
-_RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64}
+_RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_retrieval_ranks_ws_bytes': c_i64,
+             'ctclip_retrieval_topk_ws_bytes': c_i64}
 
 
 def register(name, argtypes):

@@ -1296,6 +1296,69 @@ def zero_shot(t_raw, i_raw, log_temp):
     return probs, scores
 
 
+RETRIEVAL_MAX_ROWS, RETRIEVAL_MAX_DIM, RETRIEVAL_MAX_K = 65536, 8192, 128
+
+
+def _retrieval_args(name, q, g):
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise ValueError(f'{name}: queries [N, Dl] and gallery [M, Dl], got {tuple(q.shape)} / {tuple(g.shape)}')
+    _chk(q, f'{name}: queries', F32)
+    _chk(g, f'{name}: gallery', F32)
+    if g.device != q.device:
+        raise ValueError(f'{name}: queries on {q.device}, gallery on {g.device}')
+    return q.contiguous(), g.contiguous()
+
+
+def retrieval_ranks(q, g, pair=None):
+    """0-based rank [N] int32 of each query's positive gallery row ``pair[i]`` among the M gallery rows
+    (ctclip_retrieval_ranks): raw f32 latents q [N, Dl] / g [M, Dl], l2-normalised in the kernel, scores
+    q^ . g^ in f32; rows scoring higher rank above, and of equal scores the lower gallery index.
+    ``pair=None``: the identity (needs N == M).  ``pair`` outside [0, M) raises ValueError (one host read)."""
+    N, M = q.shape[0], g.shape[0]
+    if pair is None:
+        if q.dim() == 2 and g.dim() == 2 and N != M:
+            raise ValueError(f'retrieval_ranks: pair=None pairs row i with row i, but N = {N} and M = {M}')
+    else:
+        if pair.dim() != 1 or pair.shape[0] != N or pair.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'retrieval_ranks: pair must be {N} int32 / int64 gallery indices, got '
+                             f'{tuple(pair.shape)} {pair.dtype}')
+    q, g = _retrieval_args('retrieval_ranks', q, g)
+    Dl = q.shape[1]
+    if pair is None:
+        pair = torch.arange(N, device=q.device, dtype=torch.int32)
+    else:
+        _chk(pair, 'retrieval_ranks: pair')
+        if N and (int(pair.min()) < 0 or int(pair.max()) >= M):
+            raise ValueError(f'retrieval_ranks: pair entries must lie in [0, {M})')
+        pair = pair.to(device=q.device, dtype=torch.int32).contiguous()
+    rank = torch.empty(N, device=q.device, dtype=torch.int32)
+    nbytes = 0
+    if 1 <= N <= RETRIEVAL_MAX_ROWS and 1 <= M <= RETRIEVAL_MAX_ROWS and 1 <= Dl <= RETRIEVAL_MAX_DIM:
+        nbytes = _lib.lib().ctclip_retrieval_ranks_ws_bytes(N, M, Dl)
+    ws = torch.empty(max(nbytes // 4, 4), device=q.device, dtype=F32)
+    call('ctclip_retrieval_ranks', ptr(q), ptr(g), ptr(pair), N, M, Dl, ptr(rank), ptr(ws), nbytes, stream_ptr())
+    return rank
+
+
+def retrieval_topk(q, g, k):
+    """(score [N, k] f32, idx [N, k] int32): the k best gallery rows of each query by descending score,
+    ties by ascending gallery index (ctclip_retrieval_topk); inputs as ``retrieval_ranks``.
+    1 <= k <= min(M, 128), else KernelError (CT_ESHAPE)."""
+    q, g = _retrieval_args('retrieval_topk', q, g)
+    k = int(k)
+    N, Dl = q.shape
+    M = g.shape[0]
+    score = torch.empty(N, max(k, 0), device=q.device, dtype=F32)
+    idx = torch.empty(N, max(k, 0), device=q.device, dtype=torch.int32)
+    nbytes = 0
+    if (1 <= N <= RETRIEVAL_MAX_ROWS and 1 <= M <= RETRIEVAL_MAX_ROWS and 1 <= Dl <= RETRIEVAL_MAX_DIM
+            and 1 <= k <= min(M, RETRIEVAL_MAX_K)):
+        nbytes = _lib.lib().ctclip_retrieval_topk_ws_bytes(N, M, Dl, k)
+    ws = torch.empty(max(nbytes // 4, 4), device=q.device, dtype=F32)
+    call('ctclip_retrieval_topk', ptr(q), ptr(g), N, M, Dl, k, ptr(score), ptr(idx), ptr(ws), nbytes, stream_ptr())
+    return score, idx
+
+
 def clip_scores(t_raw, i_raw, log_temp):
     B, Dl = t_raw.shape
     if i_raw.shape[0] != B:

@@ -13,6 +13,8 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.clip_infonce(text_latents, image_latents, log_temp)
     torch.ops.ctclip.clip_infonce_ex(text_views, image_views, log_temp, text_extra, image_extra,
                                      decoupled, w_main, w_multiview)   # multiview / CLOOB / DCL loss
+    torch.ops.ctclip.retrieval_ranks(queries, gallery, pair)     # rank of each query's positive
+    torch.ops.ctclip.retrieval_topk(queries, gallery, k)         # (score, idx) of the k best rows
     torch.ops.ctclip.vq_cos_argmax(x, codebook)                 # (idx int32, l2norm(x))
     torch.ops.ctclip.peg_dwconv3d(x, weight, bias, shape, mode)  # x + PEG(x), canonical rows
     torch.ops.ctclip.cpb_mlp(rel, w0, b0, w1, b1, w2, b2)        # CPB table [heads, bins]
@@ -283,6 +285,32 @@ def clip_infonce_ex(text_latents: Tensor, image_latents: Tensor, log_temp: Tenso
     loss of pair 0 + w_multiview * mean of the other pairs (scalar)."""
     return _clip_infonce_ex(text_latents, image_latents, log_temp, text_extra, image_extra, bool(decoupled),
                             float(w_main), float(w_multiview))[0]
+
+
+# ------------------------------------------------------------------------------ retrieval
+@torch.library.custom_op('ctclip::retrieval_ranks', mutates_args=(), device_types='cuda')
+def retrieval_ranks(queries: Tensor, gallery: Tensor, pair: Optional[Tensor] = None) -> Tensor:
+    """0-based rank [N] int32 of gallery row pair[i] (None: row i, N == M) for query i: raw f32 latents
+    queries [N, Dl] / gallery [M, Dl], l2-normalised in the kernel, cosine scores on the f32 matrix pipe;
+    among equal scores the lower gallery index ranks first.  Not differentiable."""
+    return K.retrieval_ranks(queries, gallery, pair)
+
+
+@retrieval_ranks.register_fake
+def _(queries, gallery, pair=None):
+    return queries.new_empty(queries.shape[0], dtype=torch.int32)
+
+
+@torch.library.custom_op('ctclip::retrieval_topk', mutates_args=(), device_types='cuda')
+def retrieval_topk(queries: Tensor, gallery: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """(score [N, k] f32, idx [N, k] int32): each query's k best gallery rows by descending cosine score,
+    ties by ascending gallery index; 1 <= k <= min(M, 128).  Inputs as retrieval_ranks.  Not differentiable."""
+    return K.retrieval_topk(queries, gallery, k)
+
+
+@retrieval_topk.register_fake
+def _(queries, gallery, k):
+    return queries.new_empty(queries.shape[0], k), queries.new_empty(queries.shape[0], k, dtype=torch.int32)
 
 
 # -------------------------------------------------------------------------- vq_cos_argmax

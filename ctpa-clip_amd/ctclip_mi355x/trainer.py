@@ -427,10 +427,33 @@ class CTClipTrainer:
         if classifier.model is not self.model:
             raise ValueError('CTClipTrainer.validate: the classifier scores another model')
         self._val_classifier = classifier
+
+        def run():
+            classifier.refresh()
+            return ZeroShotEvaluator(classifier).evaluate(volumes, labels, n_boot=n_boot, batch_size=batch_size)
+        return self._eval_pass('validate', 'validation', run)
+
+    def validate_retrieval(self, volumes, text, pair=None, ks=(1, 5, 10, 50, 100), n_boot=0, batch_size=8):
+        """Report <-> volume retrieval between steps: ``retrieval.RetrievalEvaluator(model).evaluate``'s
+        dict (both directions' ranks, Recall@K, median rank, MRR, bootstrap CIs with n_boot > 0, and
+        the latents) for ``volumes`` and the tokenised reports ``text``; ``pair`` [reports]: each
+        report's volume (None: report i belongs to volume i).
+
+        The contract is ``validate``'s: ``flush()`` first, a codebook EMA still pending afterwards
+        raises, the forwards run in eval mode under ``no_grad``, the status word is saved, cleared,
+        read and restored around the pass, ``EvalGuardError`` if the pass set any bit, the training
+        mode restored.  With world > 1 every rank calls it at the same step."""
+        from .retrieval import RetrievalEvaluator
+        return self._eval_pass('validate_retrieval', 'retrieval validation',
+                               lambda: RetrievalEvaluator(self.model).evaluate(volumes, text, pair=pair, ks=ks,
+                                                                               n_boot=n_boot, batch_size=batch_size))
+
+    def _eval_pass(self, method, what, run):
+        """``run()`` as an evaluation pass between steps (``validate`` has the contract)."""
         self.flush()
         vqs = getattr(self.model, '_vq_state', lambda: None)()
         if vqs is not None and vqs.pending_ema is not None:
-            raise RuntimeError('CTClipTrainer.validate: a codebook EMA update is still pending after flush(); the eval '
+            raise RuntimeError(f'CTClipTrainer.{method}: a codebook EMA update is still pending after flush(); the eval '
                                'forward would queue it (a collective with world > 1) -- refusing to')
         word = K.status_word(self.device) if self._guard else None
         snap = word.clone() if word is not None else None
@@ -440,8 +463,7 @@ class CTClipTrainer:
             if word is not None:
                 word.zero_()
             with torch.no_grad():
-                classifier.refresh()
-                res = ZeroShotEvaluator(classifier).evaluate(volumes, labels, n_boot=n_boot, batch_size=batch_size)
+                res = run()
             bits = int(word.item()) if word is not None else 0      # synchronises: the forwards are done
         finally:
             if word is not None:
@@ -449,7 +471,7 @@ class CTClipTrainer:
             self.model.train(was)
         if bits:
             raise EvalGuardError(
-                f'validation after step {self.steps} was flagged on the device, status {bits} '
+                f'{what} after step {self.steps} was flagged on the device, status {bits} '
                 f'({describe_status(bits)}): its scores are not reported.  The status word was restored to '
                 f'{int(snap.item())}, training is unaffected', bits=bits)
         return res

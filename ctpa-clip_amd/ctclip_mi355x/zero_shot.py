@@ -69,11 +69,8 @@ class ZeroShotClassifier:
         if ids.shape[0] != 2 * len(self.pathologies):
             raise ValueError(f'expected {2 * len(self.pathologies)} prompt rows (a present / not present pair '
                              f'per pathology), got {ids.shape[0]}')
-        m = self.model
         self._text = text
-        with torch.no_grad(), _eval(m):
-            enc = m.text_transformer(ids, attention_mask=text.attention_mask)[0]
-            self._t_raw = Fn.TextProjFn.apply(enc[:, 0, :].contiguous(), m.to_text_latent.weight)
+        self._t_raw = text_latents(self.model, text)
         return self
 
     def refresh(self):
@@ -85,11 +82,7 @@ class ZeroShotClassifier:
 
     def image_latents(self, volumes):
         """Raw projected image latents [N, Dl] (image tower + VQ + pool + to_visual_latent)."""
-        m = self.model
-        with torch.no_grad(), _eval(m):
-            pooled, pooled_b = m.visual_transformer.encode_pooled(volumes)
-            W = m.to_visual_latent.weight
-            return m._project(W, m._visual_weight_bf16(W), pooled, pooled_b)
+        return image_latents(self.model, volumes)
 
     def predict(self, volumes, batch_size=8):
         if self._t_raw is None:
@@ -115,3 +108,20 @@ class _eval:
 
     def __exit__(self, *exc):
         self.m.train(self.was)
+
+
+# the eval-mode, no-grad forwards behind ZeroShotClassifier and retrieval.RetrievalEvaluator
+def text_latents(m, text):
+    """Raw projected text latents [rows, Dl] of ``text`` (``.input_ids`` / ``.attention_mask``): BERT, the
+    CLS row, to_text_latent."""
+    with torch.no_grad(), _eval(m):
+        enc = m.text_transformer(text.input_ids, attention_mask=text.attention_mask)[0]
+        return Fn.TextProjFn.apply(enc[:, 0, :].contiguous(), m.to_text_latent.weight)
+
+
+def image_latents(m, volumes):
+    """Raw projected image latents [N, Dl] (image tower + VQ + pool + to_visual_latent)."""
+    with torch.no_grad(), _eval(m):
+        pooled, pooled_b = m.visual_transformer.encode_pooled(volumes)
+        W = m.to_visual_latent.weight
+        return m._project(W, m._visual_weight_bf16(W), pooled, pooled_b)

@@ -794,6 +794,30 @@ int ctclip_eval_volume(const ctclip_eval_volume_args* a, float* out, void* strea
 int ctclip_auroc_boot(const float* scores, const uint8_t* labels, const int32_t* order, const int32_t* resample,
                       int32_t N, int32_t P, int32_t S, double* out, void* stream);
 
+/* ---------------------------------------------------------------- retrieval evaluation (csrc/retrieval.hip)
+ * Paired ranks and top-k lists of queries q [N][Dl] against a gallery g [M][Dl], both RAW f32 latents:
+ * the kernels l2-normalise them as the loss does (sqrtf, a true division by max(norm, 1e-12): a zero row
+ * stays zero) and score S_ij = q^_i . g^_j in f32 on the matrix pipe (v_mfma_f32_16x16x4_f32, 64 x 64
+ * tiles); no temperature (it changes no ranking).  Each S_ij is one fma chain in ascending k whose bits
+ * do not depend on the tile or the place in it, so bit-equal gallery rows score bit-equal and the tie
+ * rule holds: among equal scores the lower gallery index ranks first.  The N x M matrix is never
+ * written.  No float atomics: the same bits on every run.
+ *   ranks: pair [N] int32 = the gallery row of each query's positive, in [0, M) -- the CALLER's duty
+ *     (device data; an entry outside is read as row 0, never out of bounds) -> rank [N] int32,
+ *     rank_i = #{ j != pair_i : S_ij > S_i,pair_i or (S_ij == S_i,pair_i and j < pair_i) }: the 0-based
+ *     place of the positive in a stable descending sort.  S_i,pair_i is compared in the bits of the tile
+ *     pass (the same MFMA chain run on the query and its positive).
+ *   topk: score [N][k] f32, idx [N][k] int32: the k best gallery rows of each query, by descending
+ *     score, ties by ascending gallery index.  1 <= k <= min(M, 128).
+ * ws: ctclip_retrieval_*_ws_bytes(...) bytes, 16-B aligned (0 = unsupported shape).  1 <= N, M <= 65536,
+ * 1 <= Dl <= 8192, k as above: CT_ESHAPE otherwise; a missing pointer or a short ws: CT_EINVAL. */
+int64_t ctclip_retrieval_ranks_ws_bytes(int32_t N, int32_t M, int32_t Dl);
+int ctclip_retrieval_ranks(const float* q, const float* g, const int32_t* pair, int32_t N, int32_t M, int32_t Dl,
+                           int32_t* rank, void* ws, int64_t ws_bytes, void* stream);
+int64_t ctclip_retrieval_topk_ws_bytes(int32_t N, int32_t M, int32_t Dl, int32_t k);
+int ctclip_retrieval_topk(const float* q, const float* g, int32_t N, int32_t M, int32_t Dl, int32_t k, float* score,
+                          int32_t* idx, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
