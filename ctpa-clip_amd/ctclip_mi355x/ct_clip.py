@@ -141,6 +141,29 @@ class CTCLIP(nn.Module):
         if vqs is not None:
             vqs.flush_ema()
 
+    def set_ema_mode(self, mode):
+        """What a train-mode image tower does with the codebook EMA (functional.VQState.ema_mode):
+        None updates it in every call, 'skip' withholds it, 'hold' adds the call's rows to held
+        statistics that ``apply_held_ema`` turns into ONE update (``drop_held_ema`` forgets them).
+        Returns the previous mode.  The chunked step's two passes (CTClipTrainer.train_step_chunked)."""
+        if mode not in (None, 'skip', 'hold'):
+            raise ValueError(f"CTCLIP.set_ema_mode: None, 'skip' or 'hold', got {mode!r}")
+        vqs = self._vq_state()
+        if vqs is None:
+            return None
+        old, vqs.ema_mode = vqs.ema_mode, mode
+        return old
+
+    def apply_held_ema(self):
+        vqs = self._vq_state()
+        if vqs is not None:
+            vqs.apply_held_ema()
+
+    def drop_held_ema(self):
+        vqs = self._vq_state()
+        if vqs is not None:
+            vqs.drop_held_ema()
+
     def _visual_weight_bf16(self, W):
         """bf16 to_visual_latent (or to_visual_latent_extra) weight (151 M parameters): the Adam-kept
         shadow when W trains, else a cast cached until W changes (one cache slot per weight).  Frozen

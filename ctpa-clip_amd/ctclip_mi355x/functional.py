@@ -1018,7 +1018,7 @@ class VQPoolFn(torch.autograd.Function):
             # read the pre-update codebook, beside the rest of this step
             aux = streams.aux_stream(zf.device)
 
-            def ema():
+            def ema(accum=True, apply=True):
                 # persistent statistics (2^-40 fixed-point esum), zeroed once here and then by the
                 # finalize kernel behind its reads: no fill launches per step.  bins has one slot past
                 # the C counts: this rank's step status word (a flagged forward: fp16 range, a
@@ -1026,35 +1026,47 @@ class VQPoolFn(torch.autograd.Function):
                 # statistics, so every rank drops a flagged step's codebook update together
                 bins_g, esum = state.ema_buffers(C, D, zf.device)
                 bins = bins_g[:C]
-                if zf.is_cuda:
+                if apply and zf.is_cuda:
                     # the guard: the trainer's summed skip word of this update's step when it owns the
                     # step (DEFER_EMA '2' / '3': the update may run beside the NEXT step, whose
                     # kernels may flag the live word for their own step), else the live word
                     g_src, state.ema_guard = state.ema_guard, None
                     bins_g[C:].copy_(g_src if g_src is not None else K.status_word(zf.device))
-                work = state.ema_work(C, xn.shape[0], zf.device) if _EMA_SORTED else None
-                K.vq_ema_accum(idx, xn, bins, esum, work=work)
-                dist_sync.sum_codebook_stats(bins_g, esum)
-                K.vq_ema_finalize(bins, esum, decay, cb, cluster.view(-1), cb_b, reset=True,
-                                  guard=bins_g[C:] if zf.is_cuda else None)
-            if aux is None:
-                ema()
-            else:
-                dev = zf.device
+                if accum:
+                    # (the accumulation adds onto what the buffers hold: integer counts in f32 and
+                    # fixed-point sums, so statistics held over several calls -- ema_mode 'hold' --
+                    # are the bits of one call on all their rows)
+                    work = state.ema_work(C, xn.shape[0], zf.device) if _EMA_SORTED else None
+                    K.vq_ema_accum(idx, xn, bins, esum, work=work)
+                if apply:
+                    dist_sync.sum_codebook_stats(bins_g, esum)
+                    K.vq_ema_finalize(bins, esum, decay, cb, cluster.view(-1), cb_b, reset=True,
+                                      guard=bins_g[C:] if zf.is_cuda else None)
 
-                def launch():
-                    aux.wait_stream(torch.cuda.current_stream(dev))
-                    for t in (idx, xn, cb, cluster, cb_b):
-                        t.record_stream(aux)
-                    with torch.cuda.stream(aux):
-                        ema()
-                # CTCLIP.encode defers the launch until after the image projection: the EMA's
-                # statistics pass (~0.36 ms, HBM-bound) otherwise runs beside the projection's
-                # weight stream (302 MB) and slows it by ~40 us (r05f: 98 us in step vs 56 alone)
-                if state.defer_ema:
-                    state.pending_ema = launch
-                else:
-                    launch()
+            def launch(**kw):
+                if aux is None:
+                    return ema(**kw)
+                aux.wait_stream(torch.cuda.current_stream(zf.device))
+                for t in (idx, xn, cb, cluster, cb_b):
+                    t.record_stream(aux)
+                with torch.cuda.stream(aux):
+                    ema(**kw)
+            if state.ema_mode == 'hold':
+                # the chunked step's second pass (CTClipTrainer.train_step_chunked): this call's rows
+                # are added to the statistics now, the update itself waits for apply_held_ema
+                launch(apply=False)
+                state.held_ema = lambda: launch(accum=False)
+            elif state.ema_mode == 'skip':
+                pass        # that step's first pass: the codebook is read, nothing is accumulated
+            elif aux is None:
+                ema()
+            # CTCLIP.encode defers the launch until after the image projection: the EMA's
+            # statistics pass (~0.36 ms, HBM-bound) otherwise runs beside the projection's
+            # weight stream (302 MB) and slows it by ~40 us (r05f: 98 us in step vs 56 alone)
+            elif state.defer_ema:
+                state.pending_ema = launch
+            else:
+                launch()
             state.mark_codebook_fresh(cb)
         ctx.geo = geo
         ctx.D = D
@@ -1113,6 +1125,35 @@ class VQState:
         self.defer_ema = False      # VQPoolFn leaves its EMA launch in pending_ema (CTCLIP.encode)
         self.pending_ema = None
         self.ema_guard = None       # int32[1] guard word for the pending update (CTClipTrainer)
+        # the chunked step (CTClipTrainer.train_step_chunked): None -- every training call updates the
+        # codebook; 'skip' -- a training call reads the codebook and leaves the statistics alone;
+        # 'hold' -- a training call adds its rows to the statistics, apply_held_ema updates once
+        self.ema_mode = None
+        self.held_ema = None        # the update of the statistics held so far ('hold')
+
+    def apply_held_ema(self):
+        """Make the one update of the statistics that 'hold' calls accumulated the pending one: it is
+        then queued, and guarded, as any deferred update is (``flush_ema``, ``ema_guard``)."""
+        fn, self.held_ema = self.held_ema, None
+        if fn is not None:
+            self.flush_ema()
+            self.pending_ema = fn
+
+    def drop_held_ema(self):
+        """Forget held statistics (error paths): the buffers are zeroed on the stream the updates
+        run on, ready for the next accumulation."""
+        held, self.held_ema = self.held_ema, None
+        b = getattr(self, '_ema_buf', None)
+        if held is None or b is None:
+            return
+        dev = b[0].device
+        aux = streams.aux_stream(dev)
+        if aux is None:
+            b[0].zero_(), b[1].zero_()
+            return
+        aux.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(aux):
+            b[0].zero_(), b[1].zero_()
 
     def ema_buffers(self, C, D, device):
         """(bins f32 [C + 1], esum int64 [C, D]) of the EMA update, zero between updates (created on the
@@ -1244,6 +1285,23 @@ def loss_uses_tiled(Bg):
     """Whether a gathered batch of Bg rows takes the tiled loss under the current mode."""
     mode = _LOSS_TILED['mode']
     return mode == 'always' or (mode == 'auto' and int(Bg) > LOSS_ONE_WORKGROUP_MAX)
+
+
+def clip_loss_all_rows(t_raw, i_raw, log_temp, decoupled=False):
+    """The loss of raw latents ``t_raw`` / ``i_raw`` [1, Bg, Dl] already on this device, with the
+    gradient of EVERY row from the one launch: (loss [1], dt [Bg, Dl], di [Bg, Dl], dlog_temp [1]).
+    The kernel is the one ``ClipLossFn`` / ``ClipLossExFn`` take for Bg rows (``loss_uses_tiled``; the
+    plain configuration on the one-workgroup kernel, decoupled contrastive learning on the general
+    one).  The chunked step's loss over its latent caches (CTClipTrainer.train_step_chunked)."""
+    log_temp = log_temp.detach().reshape(1).contiguous()
+    if loss_uses_tiled(t_raw.shape[1]):
+        loss, dt, di, _, _, dlt, _ = K.clip_loss_tiled(t_raw, i_raw, log_temp, decoupled=decoupled)
+    elif decoupled:
+        loss, dt, di, _, _, dlt, _ = K.clip_loss_ex(t_raw, i_raw, log_temp, decoupled=True)
+    else:
+        loss, dt, di, dlt = K.clip_loss(t_raw[0], i_raw[0], log_temp)[:4]
+        return loss, dt, di, dlt
+    return loss, dt[0], di[0], dlt
 
 
 class ClipLossFn(torch.autograd.Function):

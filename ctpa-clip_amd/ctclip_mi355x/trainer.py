@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import collections
 import os
+from types import SimpleNamespace as _Rows
 
 import torch
 
@@ -241,6 +242,10 @@ class CTClipTrainer:
         self._ln_pending = collections.deque()       # (step, event, pinned int32[1])
         self._ln_host = [torch.zeros(1, dtype=torch.int32, pin_memory=True) for _ in range(4)] if self._guard else []
         self.ln_steps_checked = 0
+        # train_step_chunked leaves its latent caches and the chunks' dropout call states here; with
+        # keep_chunk_latents also pass 2's raw latents and VQ indices per chunk (tests, diagnostics)
+        self.keep_chunk_latents = False
+        self.last_chunked = None
 
     def _local_status(self):
         """This rank's sticky LayerNorm-exchange status word (int32[1] on the device), or None (CPU)."""
@@ -571,6 +576,163 @@ class CTClipTrainer:
         finally:
             if own:
                 self.model.ema_after_step = False
+        self.optimizer_step()
+        self._queue_ln_check()
+        return loss.detach()
+
+    # ------------------------------------------------------------------ chunked step
+    def train_step_chunked(self, text, video, chunk, aug_image=None):
+        """One contrastive step on ``Bg = len(video)`` pairs whose towers run ``chunk`` pairs at a time
+        (the last chunk may be shorter): the loss and every gradient are those of the ONE batch of Bg
+        pairs -- each row's negatives are all the others -- while only one chunk's activations are
+        alive at a time.  ``video`` (int16 HU or f32) may sit in host (pinned) memory: a chunk is
+        copied to the device when its turn comes.  Returns the loss [1] over the Bg rows.
+
+        Three passes.  Pass 1 runs both towers per chunk under ``no_grad`` in train
+        mode (BERT's dropout on, the codebook read and its EMA withheld) and writes the raw latents
+        into two [1, Bg, Dl] caches.  One loss launch over the caches gives the loss, the gradient of
+        every cached row and of the temperature.  Pass 2 rewinds BERT's dropout call state to the one
+        recorded for the chunk, runs the chunk's training forward again and back-propagates its rows
+        of the cached gradients; parameter gradients add up in the arena, the codebook's EMA
+        statistics are held.  Then ONE ``optimizer_step``: one clip, one Adam, one skip word, one
+        codebook update from the held statistics.  ``self.steps`` advances by one.
+
+        A status flag raised by any chunk of either pass skips the whole step, as ``train_step``'s
+        (``check()`` raises).  Refused: torch.distributed with more than one rank, ``aug_image``,
+        ``extra_latent_projection`` (NotImplementedError); ``chunk < 1`` and differing row counts of
+        ``text`` and ``video`` (ValueError)."""
+        if aug_image is not None:
+            raise NotImplementedError('train_step_chunked: image multiview (aug_image) is not chunked; use train_step')
+        if getattr(self.model, 'extra_latent_projection', False):
+            raise NotImplementedError('train_step_chunked: extra_latent_projection=True is not chunked; use train_step')
+        if dist_sync.world_rank()[0] > 1:
+            raise NotImplementedError('train_step_chunked: one rank only (the latent caches are not gathered '
+                                      'across ranks yet)')
+        if not hasattr(self.model, 'encode') or not hasattr(self.model, 'set_ema_mode'):
+            raise NotImplementedError('train_step_chunked: needs a CTCLIP model (encode, set_ema_mode)')
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f'train_step_chunked: chunk must be at least 1, got {chunk}')
+        Bg = int(video.shape[0])
+        if int(text.input_ids.shape[0]) != Bg or Bg < 1:
+            raise ValueError(f'train_step_chunked: {int(text.input_ids.shape[0])} reports for {Bg} volumes')
+        hp = streams.main_stream(self.device)
+        if hp is None:
+            return self._train_step_chunked(text, video, chunk)
+        caller = torch.cuda.current_stream(self.device)
+        hp.wait_stream(caller)
+        with torch.cuda.stream(hp):
+            loss = self._train_step_chunked(text, video, chunk)
+        caller.wait_stream(hp)
+        loss.record_stream(caller)
+        return loss
+
+    def _chunks(self, text, video, chunk):
+        """(row0, row1, text rows, volume rows on the device) of every chunk, made as it is asked for."""
+        Bg = int(video.shape[0])
+        mask = getattr(text, 'attention_mask', None)
+        for r0 in range(0, Bg, chunk):
+            r1 = min(Bg, r0 + chunk)
+            t = _Rows(input_ids=text.input_ids[r0:r1].to(self.device, non_blocking=True),
+                      attention_mask=None if mask is None else mask[r0:r1].to(self.device, non_blocking=True))
+            yield r0, r1, t, video[r0:r1].to(self.device, non_blocking=True)
+
+    def _dropout_hooks(self):
+        tt = getattr(self.model, 'text_transformer', None)
+        return getattr(tt, 'dropout_state', None), getattr(tt, 'set_dropout_state', None)
+
+    def _chunked_pass1(self, text, video, chunk):
+        """Pass 1 of ``train_step_chunked``: (text cache, image cache [1, Bg, Dl] f32 raw latents,
+        BERT's dropout call state at the start of every chunk).  Train mode, no autograd graph, the
+        codebook EMA withheld: the codebook and its cluster sizes are left as they were."""
+        model = self.model
+        model.train()
+        get, _ = self._dropout_hooks()
+        tc = ic = None
+        states = []
+        old = model.set_ema_mode('skip')
+        try:
+            with torch.no_grad():
+                for r0, r1, t, v in self._chunks(text, video, chunk):
+                    states.append(get() if get is not None else None)
+                    _, _, t_raw, i_raw = model.encode(t, v)
+                    if tc is None:
+                        Bg = int(video.shape[0])
+                        tc = torch.empty(1, Bg, t_raw.shape[1], device=self.device, dtype=torch.float32)
+                        ic = torch.empty(1, Bg, i_raw.shape[1], device=self.device, dtype=torch.float32)
+                    tc[0, r0:r1].copy_(t_raw)
+                    ic[0, r0:r1].copy_(i_raw)
+        finally:
+            model.set_ema_mode(old)
+        return tc, ic, states
+
+    def _chunked_pass2(self, text, video, chunk, dt, di, states, keep=None):
+        """Pass 2: every chunk's training forward again, from the dropout call state recorded for it,
+        and the backward of its rows of ``dt`` / ``di`` through the raw latents -- the text tower on
+        the text stream beside the image tower, as ``forward_backward`` queues them.  The codebook's
+        EMA statistics are held (CTCLIP.set_ema_mode)."""
+        model = self.model
+        _, put = self._dropout_hooks()
+        old = model.set_ema_mode('hold')
+        model.defer_text_backward = True
+        try:
+            for c, (r0, r1, t, v) in enumerate(self._chunks(text, video, chunk)):
+                if put is not None and states[c] is not None:
+                    put(states[c])
+                _, _, t_raw, i_raw = model.encode(t, v)
+                if keep is not None:
+                    keep['pass2_text'].append(t_raw.detach().clone())
+                    keep['pass2_image'].append(i_raw.detach().clone())
+                    keep['indices'].append(model._vq_state().last_indices.clone())
+                outs = [(x, g[r0:r1]) for x, g in ((t_raw, dt), (i_raw, di)) if x.requires_grad]
+                if outs:
+                    # what the loss node's backward does in forward_backward: the towers' latents are
+                    # leaves (CTCLIP.encode), their hooks mark the gradient ready for the text stream
+                    torch.autograd.backward([x for x, _ in outs], [g for _, g in outs])
+                back_img = model.backward_deferred_image
+                if not TEXT_FIRST:
+                    back_img()
+                model.backward_deferred_text()
+                if TEXT_FIRST:
+                    back_img()
+        finally:
+            model.defer_text_backward = False
+            model.set_ema_mode(old)
+
+    def _train_step_chunked(self, text, video, chunk):
+        from . import functional as Fn
+        self._check_ln(block_upto=self.steps - 2)
+        model = self.model
+        keep = None
+        if self.keep_chunk_latents:
+            keep = {'pass2_text': [], 'pass2_image': [], 'indices': []}
+        # one status slot, one set of buckets for the whole call: nothing goes out before
+        # optimizer_step (one rank: no all-reduce to overlap), which reads the sticky status word once
+        self.grad_sync.arm()
+        dist_sync.disarm()
+        try:
+            with K.ln_guard():
+                tc, ic, states = self._chunked_pass1(text, video, chunk)
+                loss, dt, di, dlt = Fn.clip_loss_all_rows(tc, ic, model.temperature,
+                                                          bool(model.decoupled_contrastive_learning))
+                if model.temperature.requires_grad:
+                    # the temperature's gradient comes from the one loss launch, once
+                    self.flat.rebind_grads([model.temperature])
+                    model.temperature.grad.add_(dlt.reshape(()))
+                self._chunked_pass2(text, video, chunk, dt, di, states, keep)
+            model.apply_held_ema()        # pending: optimizer_step guards and queues it, as train_step's
+        except BaseException:
+            dist_sync.disarm()
+            K.discard_deferred()
+            model._deferred_text = model._deferred_image = None
+            model.drop_held_ema()
+            # a deferred text Adam of the previous step reads (and clears) its gradients: queue it first
+            streams.flush_text(self.device)
+            streams.join_text(self.device)
+            streams.join_aux(self.device)
+            self.flat.grad.zero_()
+            raise
+        self.last_chunked = dict(text_cache=tc, image_cache=ic, dropout_states=states, **(keep or {}))
         self.optimizer_step()
         self._queue_ln_check()
         return loss.detach()
