@@ -275,6 +275,7 @@ _SIGS = {
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],
     'ctclip_eval_volume': [ctypes.POINTER(EvalVolumeArgs), c_vp, c_vp],
     'ctclip_auroc_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
+    'ctclip_curve_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
     'ctclip_retrieval_ranks_ws_bytes': [c_i32, c_i32, c_i32],
     'ctclip_retrieval_ranks': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'ctclip_retrieval_topk_ws_bytes': [c_i32, c_i32, c_i32, c_i32],

@@ -402,12 +402,14 @@ class CTClipTrainer:
         also warned)."""
         return checkpoint.load(self, path, strict=strict, restore_rng=restore_rng)
 
-    def validate(self, volumes, labels, classifier=None, n_boot=0, batch_size=8):
+    def validate(self, volumes, labels, classifier=None, n_boot=0, batch_size=8, curves=False):
         """The reference trainer's validation pass between steps (CTCLIPTrainer.py:356-454): score
         ``volumes`` zero-shot with ``classifier`` (a ``zero_shot.ZeroShotClassifier`` of this model
         with its prompts set -- the reference's are ``VALIDATION_PATHOLOGIES`` with
         ``VALIDATION_TEMPLATE``; None: the one passed last time) and return
-        ``evaluate.ZeroShotEvaluator.evaluate``'s dict (probs, auroc, ci, f1_micro, flat_accuracy).
+        ``evaluate.ZeroShotEvaluator.evaluate``'s dict (probs, auroc, ci, f1_micro, flat_accuracy; with
+        ``curves=True`` also ``curves`` -- operating point, threshold, PR-AUC, average precision per
+        label -- and, with n_boot > 0, ``curves_ci``).
 
         ``flush()`` runs first, so every queued step is applied and verified (a StepGuardError raised
         here belongs to a training step).  The prompts are encoded again with the current weights,
@@ -435,7 +437,8 @@ class CTClipTrainer:
 
         def run():
             classifier.refresh()
-            return ZeroShotEvaluator(classifier).evaluate(volumes, labels, n_boot=n_boot, batch_size=batch_size)
+            return ZeroShotEvaluator(classifier).evaluate(volumes, labels, n_boot=n_boot, batch_size=batch_size,
+                                                          curves=curves)
         return self._eval_pass('validate', 'validation', run)
 
     def validate_retrieval(self, volumes, text, pair=None, ks=(1, 5, 10, 50, 100), n_boot=0, batch_size=8):

@@ -794,6 +794,21 @@ int ctclip_eval_volume(const ctclip_eval_volume_args* a, float* out, void* strea
 int ctclip_auroc_boot(const float* scores, const uint8_t* labels, const int32_t* order, const int32_t* resample,
                       int32_t N, int32_t P, int32_t S, double* out, void* stream);
 
+/* Operating point and precision-recall sums of the same S resamples x P labels (evaluate.py:104-113
+ * choose_operating_point over roc_curve, :116-118 auc(recall, precision) over precision_recall_curve,
+ * and sklearn's average_precision_score).  Inputs and refusals are ctclip_auroc_boot's.
+ * out [S][P][5] f64 = sensitivity, specificity, threshold, pr_auc, average_precision.
+ * A point is a run of bit-equal scores whose rows the resample drew at least once; the points are
+ * ranked by descending score, tp_k / fp_k the weighted positives / negatives down to point k.
+ *   operating point: the first point (descending) of maximal J_k = tp_k Neg - fp_k Pos, an exact
+ *     int64, if that maximum is > 0: sensitivity = tp / Pos, specificity = 1 - fp / Neg, threshold =
+ *     its score; otherwise 0, 0, NaN.
+ *   pr_auc = sum_k (r_k - r_{k-1}) (p_k + p_{k-1}) / 2, average_precision = sum_k (r_k - r_{k-1}) p_k,
+ *     r_k = tp_k / Pos, p_k = tp_k / (tp_k + fp_k), r_0 = 0, p_0 = 1; f64 sums in a fixed order.
+ * Pos = 0 or Neg = 0: five NaN.  Bit-reproducible; no float atomics. */
+int ctclip_curve_boot(const float* scores, const uint8_t* labels, const int32_t* order, const int32_t* resample,
+                      int32_t N, int32_t P, int32_t S, double* out, void* stream);
+
 /* ---------------------------------------------------------------- retrieval evaluation (csrc/retrieval.hip)
  * Paired ranks and top-k lists of queries q [N][Dl] against a gallery g [M][Dl], both RAW f32 latents:
  * the kernels l2-normalise them as the loss does (sqrtf, a true division by max(norm, 1e-12): a zero row
