@@ -6,3 +6,4 @@ Drop-in for the reference's ``ct_clip.CTCLIP`` / ``ct_clip.ctvit.CTViT`` /
 __version__ = '0.1.0'
 
 from . import ops  # noqa: E402,F401  (registers the torch.ops.ctclip.* custom ops)
+from .mlm import MLM  # noqa: E402,F401

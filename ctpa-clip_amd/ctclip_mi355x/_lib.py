@@ -154,6 +154,18 @@ class ClipLossTiledArgs(ctypes.Structure):
     _fields_ = ClipLossExArgs._fields_[:-1] + [('ws_bytes', c_i64), ('grad_row0', c_i32), ('grad_rows', c_i32)]
 
 
+class MlmMaskArgs(ctypes.Structure):
+    """ctclip_mlm_mask_args (include/ctclip_hip.h): the masked-language-model mask kernel."""
+    _fields_ = [
+        ('ids', c_vp), ('B', c_i32), ('L', c_i32),
+        ('num_tokens', c_i64), ('mask_token_id', c_i64), ('pad_token_id', c_i64),
+        ('ignore', c_i64 * 32), ('n_ignore', c_i32), ('m_max', c_i32),
+        ('mask_prob', ctypes.c_double), ('replace_prob', ctypes.c_double), ('random_token_prob', ctypes.c_double),
+        ('seed', ctypes.c_uint64),
+        ('masked_ids', c_vp), ('labels', c_vp), ('sel', c_vp),
+    ]
+
+
 # name -> argtypes (restype is int32 unless _RESTYPES names another)
 _SIGS = {
     'ctclip_version': [],
@@ -280,6 +292,11 @@ _SIGS = {
     'ctclip_retrieval_ranks': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'ctclip_retrieval_topk_ws_bytes': [c_i32, c_i32, c_i32, c_i32],
     'ctclip_retrieval_topk': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
+    'ctclip_mlm_mask': [ctypes.POINTER(MlmMaskArgs), c_vp],
+    'ctclip_mlm_gather': [c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
+    'ctclip_mlm_ce_ws_bytes': [c_i32],
+    'ctclip_mlm_ce': [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
+    'ctclip_mlm_scatter': [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp],
     'ctclip_sgemm': [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
                      c_i32, c_f32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp],
     'ctclip_embed_fwd': [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -290,7 +307,7 @@ _SIGS = {
                     c_vp, c_vp],
 }
 _RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_retrieval_ranks_ws_bytes': c_i64,
-             'ctclip_retrieval_topk_ws_bytes': c_i64}
+             'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64}
 
 
 def register(name, argtypes):

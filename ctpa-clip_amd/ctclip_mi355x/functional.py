@@ -1523,3 +1523,59 @@ class BertLayerFn(torch.autograd.Function):
             for i, (W, b) in enumerate(((Wq, bq), (Wk, bk), (Wv, bv))):
                 wgrad(dqkv[:, i * Hd:(i + 1) * Hd], xb, W, b)
         return (dx, None, None, None, None, None, None) + (None,) * 18
+
+
+# ----------------------------------------------------------------------------- masked language modelling
+def mlm_weight(W, b):
+    """(bf16 hi shadow, bf16 lo shadow [Vp, D], f32 bias [Vp]) of the MLM head's ``to_logits`` for the GEMMs,
+    Vp = V rounded up to 8 with zero pad rows / entries (kernels.mlm_pad_cols: V = 30,522 is no multiple of
+    the GEMM's 16-byte row chunk; padded shadows keep every GEMM on the existing aligned paths, and the loss
+    kernel never reads the pad columns).  hi + lo = W to ~16 mantissa bits, as the text tower's forward
+    weights (bf_split).  Cached on the parameters until they change (optimizer epoch, version, storage)."""
+    V, D = W.shape
+    Vp = K.mlm_pad_cols(V)
+    key = (K.weights_epoch(), W._version, W.data_ptr(), b._version, b.data_ptr())
+    e = W.__dict__.get('_ctclip_mlm')
+    if e is None or e[0] != key:
+        hi = torch.zeros(Vp, D, device=W.device, dtype=BF16)
+        lo = torch.zeros(Vp, D, device=W.device, dtype=BF16)
+        K.cast_bf16_split(W.detach().contiguous(), hi=hi[:V], lo=lo[:V])
+        bp = K.pack_rows_f32(b.detach().view(1, V), 1, Vp)
+        e = (key, hi, lo, bp.view(Vp))
+        W.__dict__['_ctclip_mlm'] = e
+    return e[1], e[2], e[3]
+
+
+class MlmHeadFn(torch.autograd.Function):
+    """Cross-entropy of ``to_logits`` over the selected positions only (ct_clip/mlm.py:100-107 with
+    ignore_index = pad): hidden [B, L, D] f32, sel [M] int32 flat positions (-1: unused slot), labels
+    [B, L] int64.  The logits, their gradient and the three backward GEMMs have M = B * ceil(p L) rows, never
+    B * L; with no valid row the loss is NaN, as F.cross_entropy's.  The forward GEMM reads both operands as
+    hi + lo bf16 pairs; the backward (dH, dW on the existing GEMMs, db a column sum) reads the bf16 images of
+    the logit gradient, the selected rows and the weight, like the rest of the text tower's backward."""
+
+    @staticmethod
+    def forward(ctx, hidden, sel, labels, W, b):
+        D = hidden.shape[-1]
+        h2 = hidden.detach().reshape(-1, D)
+        wp, wp_lo, bp = mlm_weight(W, b)
+        loss, _, hsel, _, dlog, dlb = K.mlm_head_fwd(h2, sel, labels.reshape(-1), wp, wp_lo, bp, W.shape[0])
+        ctx.save_for_backward(hsel, dlog, dlb, wp, sel)
+        ctx.shape = tuple(hidden.shape)
+        ctx.V = W.shape[0]
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        hsel, dlog, dlb, wp, sel = ctx.saved_tensors
+        s = dloss.reshape(1)
+        V, D = ctx.V, ctx.shape[-1]
+        dh = dW = db = None
+        if ctx.needs_input_grad[0]:
+            dsel = K.matmul_nn(dlb, wp, out_dtype=F32) * s
+            dh = K.mlm_scatter(dsel, sel, math.prod(ctx.shape[:-1])).view(ctx.shape)
+        if ctx.needs_input_grad[3]:
+            dW = K.matmul_tn(dlb, hsel)[:V] * s
+        if ctx.needs_input_grad[4]:
+            db = K.colsum(dlog)[:V] * s
+        return dh, None, None, dW, db

@@ -1359,6 +1359,100 @@ def retrieval_topk(q, g, k):
     return score, idx
 
 
+# ----------------------------------------------------------------------------- masked language modelling
+MLM_MAX_LEN, MLM_MAX_IGNORE = 512, 32
+
+
+def mlm_m_max(mask_prob, L):
+    """Slots per row of the selection list: ceil(mask_prob * L), ct_clip/mlm.py's ``max_masked``."""
+    import math
+    return int(math.ceil(float(mask_prob) * int(L)))
+
+
+def mlm_pad_cols(V):
+    """Row length of the logits buffer and rows of the padded weight shadow: V rounded up to the GEMM's
+    8-column (16-byte) chunk."""
+    return (int(V) + 7) // 8 * 8
+
+
+def mlm_mask(ids, *, seed, mask_prob, replace_prob, random_token_prob, num_tokens, mask_token_id, pad_token_id,
+             ignore_ids=()):
+    """(masked_ids [B, L] int64, labels [B, L] int64, sel [B * m_max] int32) of token ids [B, L] (ctclip_mlm_mask):
+    per row ceil(mask_prob * n_b) of the n_b positions whose id is neither pad nor in ``ignore_ids`` are
+    selected by hash rank; ``sel`` lists their flat indices b * L + l, m_max = ceil(mask_prob * L) slots per
+    row, unused slots -1."""
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'mlm_mask: token ids [B, L] int32 / int64, got {tuple(ids.shape)} {ids.dtype}')
+    _chk(ids, 'mlm_mask: ids')
+    B, L = ids.shape
+    m_max = mlm_m_max(mask_prob, L)
+    ign = sorted({int(i) for i in ignore_ids} - {int(pad_token_id)})
+    if not (1 <= L <= MLM_MAX_LEN and B >= 1):
+        raise ValueError(f'mlm_mask: 1 <= L <= {MLM_MAX_LEN} and B >= 1, got B = {B}, L = {L}')
+    if m_max < 1:
+        raise ValueError(f'mlm_mask: mask_prob = {mask_prob} selects no position of {L}')
+    if len(ign) > MLM_MAX_IGNORE:
+        raise ValueError(f'mlm_mask: at most {MLM_MAX_IGNORE} ignored ids besides pad, got {len(ign)}')
+    ids = ids.to(torch.int64).contiguous()
+    masked = torch.empty_like(ids)
+    labels = torch.empty_like(ids)
+    sel = torch.empty(B * m_max, device=ids.device, dtype=torch.int32)
+    a = _lib.MlmMaskArgs()
+    a.ids, a.B, a.L = ptr(ids), B, L
+    a.num_tokens, a.mask_token_id, a.pad_token_id = int(num_tokens), int(mask_token_id), int(pad_token_id)
+    for i, v in enumerate(ign):
+        a.ignore[i] = v
+    a.n_ignore, a.m_max = len(ign), m_max
+    a.mask_prob, a.replace_prob, a.random_token_prob = float(mask_prob), float(replace_prob), float(random_token_prob)
+    a.seed = int(seed) & (2 ** 64 - 1)
+    a.masked_ids, a.labels, a.sel = ptr(masked), ptr(labels), ptr(sel)
+    call('ctclip_mlm_mask', _lib.ctypes.byref(a), stream_ptr())
+    return masked, labels, sel
+
+
+def mlm_head_fwd(hidden, sel, labels, wp, wp_lo, bias_p, V):
+    """The row-compacted MLM head.  hidden [R, D] f32, sel [M] int32 flat row indices (-1: unused slot),
+    labels [R] int64, wp / wp_lo [Vp, D] the bf16 hi / lo shadows of the weight padded with zero rows to
+    Vp = mlm_pad_cols(V), bias_p [Vp] f32 padded with zeros.  Returns (loss [1], count [1], hsel [M, D] bf16,
+    hsel_lo [M, D] bf16, dlogits [M, Vp] f32, dlogits_b [M, Vp] bf16): the logits exist for the M listed
+    rows only -- hsel (wp + wp_lo)^T + hsel_lo wp^T + bias, both operands to ~16 mantissa bits -- and that
+    buffer comes back overwritten with the gradient (softmax - onehot) / count (ctclip_mlm_ce)."""
+    _chk(hidden, 'mlm_head_fwd: hidden', F32)
+    _chk(sel, 'mlm_head_fwd: sel', torch.int32)
+    _chk(labels, 'mlm_head_fwd: labels', torch.int64)
+    _chk(wp, 'mlm_head_fwd: weight shadow', BF16)
+    _chk(wp_lo, 'mlm_head_fwd: weight lo shadow', BF16)
+    _chk(bias_p, 'mlm_head_fwd: bias', F32)
+    R, D = hidden.shape
+    M, Vp = sel.numel(), mlm_pad_cols(V)
+    if (tuple(wp.shape) != (Vp, D) or tuple(wp_lo.shape) != (Vp, D) or bias_p.numel() != Vp or labels.numel() != R
+            or M < 1):
+        raise ValueError(f'mlm_head_fwd: hidden {tuple(hidden.shape)}, sel {M}, labels {labels.numel()}, weight '
+                         f'{tuple(wp.shape)} / {tuple(wp_lo.shape)} (expected {(Vp, D)}), bias {bias_p.numel()}')
+    hidden, sel, labels = hidden.contiguous(), sel.contiguous(), labels.contiguous().view(-1)
+    hsel = torch.empty(M, D, device=hidden.device, dtype=BF16)
+    hsel_lo = torch.empty(M, D, device=hidden.device, dtype=BF16)
+    call('ctclip_mlm_gather', ptr(hidden), D, R, ptr(sel), M, D, ptr(hsel), ptr(hsel_lo), D, stream_ptr())
+    logits = linear(hsel, wp, bias=bias_p, out_dtype=F32, w_lo=wp_lo)
+    linear(hsel_lo, wp, out=logits, accumulate=True)
+    dlb = torch.empty(M, Vp, device=hidden.device, dtype=BF16)
+    loss = torch.empty(1, device=hidden.device, dtype=F32)
+    count = torch.empty(1, device=hidden.device, dtype=F32)
+    nbytes = _lib.lib().ctclip_mlm_ce_ws_bytes(M)
+    ws = torch.empty(max(nbytes // 4, 4), device=hidden.device, dtype=F32)
+    call('ctclip_mlm_ce', ptr(logits), ptr(dlb), Vp, ptr(sel), ptr(labels), R, M, int(V), ptr(loss), ptr(count),
+         ptr(ws), nbytes, stream_ptr())
+    return loss, count, hsel, hsel_lo, logits, dlb
+
+
+def mlm_scatter(dsel, sel, R):
+    """dH [R, D] f32: zero, except rows sel[m] = dsel[m] (ctclip_mlm_scatter)."""
+    M, D = dsel.shape
+    dh = torch.empty(R, D, device=dsel.device, dtype=F32)
+    call('ctclip_mlm_scatter', ptr(dsel), dsel.stride(0), ptr(sel), M, D, ptr(dh), D, R, stream_ptr())
+    return dh
+
+
 def clip_scores(t_raw, i_raw, log_temp):
     B, Dl = t_raw.shape
     if i_raw.shape[0] != B:

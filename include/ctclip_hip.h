@@ -833,6 +833,59 @@ int64_t ctclip_retrieval_topk_ws_bytes(int32_t N, int32_t M, int32_t Dl, int32_t
 int ctclip_retrieval_topk(const float* q, const float* g, int32_t N, int32_t M, int32_t Dl, int32_t k, float* score,
                           int32_t* idx, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- masked language modelling (csrc/mlm.hip)
+ * The token-level loss of ct_clip/mlm.py on the text tower: a mask kernel, and a cross-entropy head over the
+ * SELECTED rows only (M = B * m_max of the B * L hidden rows); the logits GEMM and the three backward GEMMs
+ * are ctclip_gemm calls on the buffers below.  Every kernel has a fixed reduction order and no float
+ * atomics: the same inputs give the same bits.
+ *
+ * Hash stream: h(s, i) = fmix64((seed ^ s * 0xBF58476D1CE4E5B9) ^ i * 0x9E3779B97F4A7C15) with murmur3's
+ * 64-bit finaliser (the one of the hidden-state dropout), i = b * L + l, u(s, i) = h(s, i) >> 32.
+ *
+ * ctclip_mlm_mask, one workgroup per sequence, 1 <= L <= 512:
+ *   a position is eligible when its id is neither pad_token_id nor one of ignore[0 .. n_ignore); n_b counts
+ *   a row's eligible positions and c_b = min(ceil(mask_prob * n_b) in double, m_max) of them are selected:
+ *   those of rank < c_b by (u(0, i), l) ascending.  labels = the id at selected positions, pad_token_id
+ *   elsewhere.  masked_ids = ids, except: with random_token_prob > 0 EVERY position (ct_clip/mlm.py:83-90)
+ *   with u(2, i) < floor(random_token_prob * 2^32) draws tok = (u(3, i) * num_tokens) >> 32 and, unless tok
+ *   is pad or ignored, takes it and leaves the mask set; a selected position still in the mask set with
+ *   u(1, i) < floor(replace_prob * 2^32) becomes mask_token_id.  sel [B][m_max]: slot r of row b holds the
+ *   flat index b * L + l of the selected position of rank r, slots r >= c_b hold -1.
+ *   CT_ESHAPE: L, B, m_max (1 <= m_max <= L), n_ignore (<= 32) or B * L (< 2^31) out of range; CT_EINVAL: a
+ *   missing pointer, a probability outside [0, 1] or num_tokens < 1. */
+typedef struct {
+  const int64_t* ids;        /* [B][L] */
+  int32_t B, L;
+  int64_t num_tokens, mask_token_id, pad_token_id;
+  int64_t ignore[32];
+  int32_t n_ignore;
+  int32_t m_max;
+  double mask_prob, replace_prob, random_token_prob;
+  uint64_t seed;
+  int64_t* masked_ids;       /* [B][L] */
+  int64_t* labels;           /* [B][L] */
+  int32_t* sel;              /* [B][m_max] */
+} ctclip_mlm_mask_args;
+int ctclip_mlm_mask(const ctclip_mlm_mask_args* a, void* stream);
+/* out [M][ldo] bf16 = hidden [R][ldh] f32 rows sel[m]; a slot outside [0, R) gives a zero row.  out_lo
+ * (optional, same layout): bf16(x - bf16(x)), the part of each value out drops.  D % 8 == 0. */
+int ctclip_mlm_gather(const float* hidden, int64_t ldh, int64_t R, const int32_t* sel, int32_t M, int32_t D,
+                      void* out, void* out_lo, int64_t ldo, void* stream);
+/* Cross-entropy over the rows of logits [M][ld] f32 (columns < V; ld >= V, ld % 8 == 0).  Row m is VALID when
+ * sel[m] is in [0, R) and labels[sel[m]] in [0, V).  Per valid row one pass over V gives the f32 log-sum-exp
+ * (running maximum subtracted); *loss = sum of (lse - logit[label]) over the valid rows / count, *count = the
+ * number of valid rows (f32); NaN when there is none, as F.cross_entropy over ignored targets only.  The row
+ * is then OVERWRITTEN with its gradient (softmax - onehot) / count, columns >= V and invalid rows with zero,
+ * and dlogits_bf16 [M][ld] gets the same values rounded to bf16 (the backward GEMMs' operand).
+ * ws: ctclip_mlm_ce_ws_bytes(M) bytes, 16-B aligned.  1 <= M <= 2^20, 1 <= V < 2^31: CT_ESHAPE otherwise. */
+int64_t ctclip_mlm_ce_ws_bytes(int32_t M);
+int ctclip_mlm_ce(float* logits, void* dlogits_bf16, int64_t ld, const int32_t* sel, const int64_t* labels, int64_t R,
+                  int32_t M, int32_t V, float* loss, float* count, void* ws, int64_t ws_bytes, void* stream);
+/* dh [R][D] f32 (ldh == D) = 0, then dh[sel[m]] = dsel[m] for the slots in [0, R) (plain stores: the mask
+ * kernel's slots are distinct; with duplicates one of them wins).  D % 4 == 0. */
+int ctclip_mlm_scatter(const float* dsel, int64_t lds, const int32_t* sel, int32_t M, int32_t D, float* dh,
+                       int64_t ldh, int64_t R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
