@@ -7,3 +7,4 @@ __version__ = '0.1.0'
 
 from . import ops  # noqa: E402,F401  (registers the torch.ops.ctclip.* custom ops)
 from .mlm import MLM  # noqa: E402,F401
+from .attribution import ZeroShotAttribution, to_volume  # noqa: E402,F401

@@ -284,6 +284,8 @@ _SIGS = {
     'ctclip_clip_loss_tiled_ws_bytes': [ctypes.POINTER(ClipLossTiledArgs)],
     'ctclip_clip_scores': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp],
     'ctclip_zero_shot': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    'ctclip_attr_weights': [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp],
+    'ctclip_attr_map': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp],
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],
     'ctclip_eval_volume': [ctypes.POINTER(EvalVolumeArgs), c_vp, c_vp],
     'ctclip_auroc_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],

@@ -1296,6 +1296,56 @@ def zero_shot(t_raw, i_raw, log_temp):
     return probs, scores
 
 
+ATTR_MAX_ROWS = 48      # CTCLIP_ATTR_MAX_ROWS of include/ctclip_hip.h
+
+
+def attr_weights(dirs, Wb, HW, D):
+    """V [R, HW, D] f32 = dirs [R, Dl] f32 . Wb [Dl, HW * D] (the bf16 ``to_visual_latent`` weight the
+    projection reads), one pass over Wb (ctclip_attr_weights).  R <= ATTR_MAX_ROWS, else KernelError
+    (CT_ESHAPE)."""
+    _chk(dirs, 'attr_weights: dirs', F32)
+    _chk(Wb, 'attr_weights: Wb', BF16)
+    if dirs.dim() != 2 or Wb.dim() != 2 or Wb.shape != (dirs.shape[1], HW * D):
+        raise ValueError(f'attr_weights: dirs [R, Dl] and Wb [Dl, {HW} * {D}], got {tuple(dirs.shape)} / '
+                         f'{tuple(Wb.shape)}')
+    dirs, Wb = dirs.contiguous(), Wb.contiguous()
+    R, Dl = dirs.shape
+    V = torch.empty(R, HW, D, device=dirs.device, dtype=F32)
+    call('ctclip_attr_weights', ptr(dirs), ptr(Wb), R, Dl, HW * D, ptr(V), stream_ptr())
+    return V
+
+
+def attr_map(V, idx, codebook, B, T, HW, i_raw=None, log_temp=None):
+    """out [B, R, T, HW] f32: out[n, r, t, hw] = s_n V[r, hw] . codebook[idx[n, t, hw]] (ctclip_attr_map),
+    V [R, HW, D] from ``attr_weights``, idx the int32 indices ``vq_pool`` reads, codebook [codes, D] f32.
+    With ``i_raw`` [B, Dl] (the raw image latents ``zero_shot`` receives) and ``log_temp`` [1]:
+    s_n = exp(log_temp) / (T ||i_raw[n]||), computed in the kernel; without: s_n = 1."""
+    _chk(V, 'attr_map: V', F32)
+    _chk(idx, 'attr_map: idx', torch.int32)
+    _chk(codebook, 'attr_map: codebook', F32)
+    if V.dim() != 3 or codebook.dim() != 2 or V.shape[1] != HW or V.shape[2] != codebook.shape[1]:
+        raise ValueError(f'attr_map: V [R, {HW}, D] and codebook [codes, D], got {tuple(V.shape)} / '
+                         f'{tuple(codebook.shape)}')
+    if idx.numel() != B * T * HW:
+        raise ValueError(f'attr_map: {B} x {T} x {HW} indices, got {idx.numel()}')
+    if (i_raw is None) != (log_temp is None):
+        raise ValueError('attr_map: i_raw and log_temp come together')
+    V, idx, codebook = V.contiguous(), idx.contiguous(), codebook.contiguous()
+    R, _, D = V.shape
+    Dl = 0
+    if i_raw is not None:
+        _chk(i_raw, 'attr_map: i_raw', F32)
+        _chk(log_temp, 'attr_map: log_temp', F32)
+        if i_raw.dim() != 2 or i_raw.shape[0] != B:
+            raise ValueError(f'attr_map: i_raw [{B}, Dl], got {tuple(i_raw.shape)}')
+        i_raw, log_temp = i_raw.contiguous(), log_temp.contiguous()
+        Dl = i_raw.shape[1]
+    out = torch.empty(B, R, T, HW, device=V.device, dtype=F32)
+    call('ctclip_attr_map', ptr(V), ptr(idx), ptr(codebook), codebook.shape[0], B, R, T, HW, D, ptr(i_raw), Dl,
+         ptr(log_temp), ptr(out), stream_ptr())
+    return out
+
+
 RETRIEVAL_MAX_ROWS, RETRIEVAL_MAX_DIM, RETRIEVAL_MAX_K = 65536, 8192, 128
 
 

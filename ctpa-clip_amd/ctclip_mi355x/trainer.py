@@ -456,6 +456,28 @@ class CTClipTrainer:
                                lambda: RetrievalEvaluator(self.model).evaluate(volumes, text, pair=pair, ks=ks,
                                                                                n_boot=n_boot, batch_size=batch_size))
 
+    def attribute(self, volumes, classifier=None, **kw):
+        """Zero-shot attribution maps between steps: ``classifier.attribute(volumes, **kw)``'s dict
+        (maps, probs, scores; ``attribution.ZeroShotAttribution.maps``) with the prompts encoded again
+        for the current weights.  ``classifier``: as in ``validate`` (None: the one passed last time).
+
+        The contract is ``validate``'s: ``flush()`` first, eval mode under ``no_grad``, the status word
+        saved, cleared, read and restored around the pass, ``EvalGuardError`` if the pass set any bit
+        (e.g. a non-finite volume), the training mode restored.  With world > 1 every rank calls it at
+        the same step."""
+        if classifier is None:
+            classifier = getattr(self, '_val_classifier', None)
+            if classifier is None:
+                raise ValueError('CTClipTrainer.attribute: pass classifier= (a ZeroShotClassifier with prompts set)')
+        if classifier.model is not self.model:
+            raise ValueError('CTClipTrainer.attribute: the classifier scores another model')
+        self._val_classifier = classifier
+
+        def run():
+            classifier.refresh()
+            return classifier.attribute(volumes, **kw)
+        return self._eval_pass('attribute', 'attribution', run)
+
     def _eval_pass(self, method, what, run):
         """``run()`` as an evaluation pass between steps (``validate`` has the contract)."""
         self.flush()

@@ -95,6 +95,15 @@ class ZeroShotClassifier:
             scores.append(s)
         return torch.cat(probs), torch.cat(scores)
 
+    def attribute(self, volumes, **kw):
+        """``attribution.ZeroShotAttribution(self).maps(volumes, **kw)``: dict(maps, probs, scores), the
+        exact split of each pathology's log-odds over the (t, h, w) token grid (the object, with its
+        cached direction weights, is kept)."""
+        from .attribution import ZeroShotAttribution
+        if getattr(self, '_attribution', None) is None:
+            self._attribution = ZeroShotAttribution(self)
+        return self._attribution.maps(volumes, **kw)
+
 
 class _eval:
     """Eval mode for the duration (the VQ codebook must not EMA-update during inference)."""

@@ -695,6 +695,34 @@ int ctclip_clip_scores(const float* t_raw, const float* i_raw, int32_t B, int32_
 int ctclip_zero_shot(const float* t_raw, const float* i_raw, int32_t P, int32_t N, int32_t Dl, const float* log_temp,
                      float* scores, float* probs, void* stream);
 
+/* ---------------------------------------------------------------- zero-shot attribution maps (csrc/attr.hip)
+ * The split of ctclip_zero_shot's scores over the (t, h, w) token grid.  The image latent is linear in
+ * the quantised tokens -- mean over t and flatten (h, w, d), ct_clip/ct_clip.py:724,740, then the
+ * bias-less to_visual_latent, :767 -- so for a direction d in latent space (a row of the l2-normalised
+ * prompt latents, :771, or the difference of a pair, whose product with the normalised image latent
+ * times the temperature is a score / the log-odds of :805-807 and ctclip_inference.py:305-315)
+ *   d . v_n = sum_{t,hw} (1/T) V[hw] . C[idx[n][t*HW+hw]],   V[hw] = W[:, hw*D:(hw+1)*D]^T d,
+ * with nothing left over.  Both entries run on the f32 matrix pipe: every output is one f32 fma chain
+ * in a fixed order.  No float atomics, nothing allocated, the same bits on every call. */
+#define CTCLIP_ATTR_MAX_ROWS 48
+/* V [R][K] f32 = dirs [R][Dl] f32 . w_bf16 [Dl][K] (the bf16 image of to_visual_latent.weight that
+ * ctclip_skinny_gemm reads, K = HW * D), f32 accumulation in ascending Dl order, one pass over w_bf16.
+ * 1 <= R <= CTCLIP_ATTR_MAX_ROWS, Dl % 16 == 0, K % 8 == 0: CT_ESHAPE otherwise; 16-byte aligned
+ * pointers (CT_EALIGN), none NULL (CT_EINVAL). */
+int ctclip_attr_weights(const float* dirs, const void* w_bf16, int32_t R, int32_t Dl, int64_t K, float* V,
+                        void* stream);
+/* out [N][R][T][HW] f32 = s_n sum_d V[r][hw*D + d] codebook[idx[n][t*HW+hw]][d]; idx is ctclip_vq_pool's
+ * int32 layout, codebook [codes][D] f32 (an index outside [0, codes) is read as row 0, never out of
+ * bounds).  i_raw != NULL: s_n = exp(*log_temp) / (T max(||i_raw[n]||, 1e-12)) with i_raw [N][Dl] the raw
+ * image latents ctclip_zero_shot receives and log_temp a device pointer -- the sum of out[n][r] over
+ * (t, hw) is then temp dirs[r] . i_raw[n] / ||i_raw[n]||.  i_raw == NULL: s_n = 1 (raw contributions).
+ * Each output element is written once.  D % 32 == 0 and 32 <= D <= 512, 1 <= R <= CTCLIP_ATTR_MAX_ROWS,
+ * N, T, HW, codes >= 1, N * T * HW < 2^31: CT_ESHAPE otherwise; V, codebook, out 16-byte aligned
+ * (CT_EALIGN); a NULL V / idx / codebook / out, or i_raw without log_temp: CT_EINVAL. */
+int ctclip_attr_map(const float* V, const int32_t* idx, const float* codebook, int32_t codes, int32_t N, int32_t R,
+                    int32_t T, int32_t HW, int32_t D, const float* i_raw, int32_t Dl, const float* log_temp,
+                    float* out, void* stream);
+
 /* ---------------------------------------------------------------- small exact-f32 GEMM (strided)
  * CPB MLP (attention.py:247-252,271-274) and its backward; act 1 = LeakyReLU(slope),
  * act 2 = multiply by LeakyReLU'(aux).  split > 1 splits K over `split` workgroup layers writing
