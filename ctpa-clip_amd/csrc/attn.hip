@@ -291,7 +291,7 @@ __device__ __forceinline__ void load_tables(const AP& p, char* tab, int Lp, int 
 // span (2 scale ||q|| max||k|| + bias range) stays <= 64, so no probability can underflow more
 // than exp2(-64) below the row's largest; otherwise that group runs the online-max code.  Same
 // softmax in exact arithmetic, f32-level differences in rounding.
-// A/B build switch (tools/attn_lazy_ab.py): 1 = the swizzled 64-B-row K / V images for head dim 32.
+// A/B build switch: 1 = the swizzled 64-B-row K / V images for head dim 32.
 // Measured 1.2 % SLOWER in this VALU-bound kernel (profiles/r04h_attn_lazy_ab.log: 252.4 vs 249.5 us),
 // so the padded 80-B rows stay the default
 #ifndef CTCLIP_ATTN_FWD_SWZ
@@ -600,7 +600,7 @@ __global__ __launch_bounds__(W * 64) void attn_fwd_kernel(AP p) {
             cmax = fmaxf(cmax, x);
           }
         }
-        // lazy rescale (p.lazy > 0, CTCLIP_ATTN_LAZY, default 16): the running max only moves when
+        // lazy rescale (p.lazy = 16): the running max only moves when
         // some lane's chunk max exceeds it by more than p.lazy (log2 units), so after the first
         // chunks the wave skips the alpha exp2, the lsum and the o rescale; probabilities stay <= 2^p.lazy (f32 sums,
         // bf16 P operands: no range issue), and lse = m + log2(lsum) is exact either way.
@@ -1772,8 +1772,7 @@ int fill(AP& p, const ctclip_attn_args* a) {
   p.drop_scale = p.drop_p > 0.f ? 1.f / (1.f - p.drop_p) : 1.f;
   p.thresh = (unsigned)std::min(4294967295.0, (double)p.drop_p * 4294967296.0);
   p.seed = a->dropout_seed;
-  static const float lazy = [] { const char* e = getenv("CTCLIP_ATTN_LAZY"); return e ? (float)atof(e) : 16.f; }();
-  p.lazy = lazy;
+  p.lazy = 16.f;
   p.L = a->L; p.H = a->H; p.nseq = a->nseq; p.M = a->M;
   p.Hg = a->grid_h; p.Wg = a->grid_w;
   p.nbins = (2 * a->grid_h - 1) * (2 * a->grid_w - 1);
@@ -1802,25 +1801,22 @@ size_t table_bytes(const AP& p, int Lp, bool bins) {
   return b;
 }
 
-int g_fwd_qb = -1;
-// static-bound softmax in the QB = 3 forward (CTCLIP_ATTN_FWD_SMAX=1): measured SLOWER at the base
+int g_fwd_qb = 3;
+// static-bound softmax in the QB = 3 forward (ctclip_attn_set_fwd_smax): measured SLOWER at the base
 // shape, 254 vs 235 us per layer (profiles/r03d_attnsmax_ab.log) -- its per-workgroup prologue (the
 // key norms and bias-table range over 576 rows + 2,209 bins, a block reduction and a barrier for
 // each of 1,536 workgroups) costs more than the per-chunk max / rescale it removes -- so off
-int g_fwd_smax = -1;
-// the C-init score chain (attn_fwd_kernel CINIT; CTCLIP_ATTN_FWD_CINIT=0 restores the round-5 kernel)
-int g_fwd_cinit = -1;
+int g_fwd_smax = 0;
+// the C-init score chain (attn_fwd_kernel CINIT; ctclip_attn_set_fwd_cinit(0) restores the round-5 kernel)
+int g_fwd_cinit = 1;
 
 template <int D>
 void launch_fwd(const AP& p, dim3 grid, size_t lds, hipStream_t st) {
   if constexpr (D == 32) {
     if (run_ok(p)) {
-      // query blocks processed together per wave (1 = the r02 kernel): CTCLIP_ATTN_FWD_QB or
-      // ctclip_attn_set_fwd_qb (A/B, bit-identical results)
-      if (g_fwd_qb < 0) { const char* e = getenv("CTCLIP_ATTN_FWD_QB"); g_fwd_qb = e ? atoi(e) : 3; }
+      // query blocks processed together per wave (1 = the r02 kernel): ctclip_attn_set_fwd_qb
+      // (A/B, bit-identical results)
       const int qb = g_fwd_qb;
-      if (g_fwd_smax < 0) { const char* e = getenv("CTCLIP_ATTN_FWD_SMAX"); g_fwd_smax = e ? atoi(e) != 0 : 0; }
-      if (g_fwd_cinit < 0) { const char* e = getenv("CTCLIP_ATTN_FWD_CINIT"); g_fwd_cinit = e ? atoi(e) != 0 : 1; }
       if (qb == 3 && g_fwd_smax)
         hipLaunchKernelGGL((attn_fwd_kernel<D, true, 12, true, 3, true>), grid, dim3(12 * 64), lds, st, p);
       else if (qb == 3 && g_fwd_cinit)
@@ -2335,21 +2331,18 @@ extern "C" int ctclip_attn_bwd(const ctclip_attn_args* a, void* stream) {
 // diagnostic: query blocks per wave of the spatial forward kernel (1, 2 or 3; results are
 // bit-identical); returns the previous setting
 extern "C" int ctclip_attn_set_fwd_smax(int on) {
-  if (g_fwd_smax < 0) { const char* e = getenv("CTCLIP_ATTN_FWD_SMAX"); g_fwd_smax = e ? atoi(e) != 0 : 0; }
   const int old = g_fwd_smax;
   g_fwd_smax = on != 0;
   return old;
 }
 
 extern "C" int ctclip_attn_set_fwd_cinit(int on) {
-  if (g_fwd_cinit < 0) { const char* e = getenv("CTCLIP_ATTN_FWD_CINIT"); g_fwd_cinit = e ? atoi(e) != 0 : 1; }
   const int old = g_fwd_cinit;
   g_fwd_cinit = on != 0;
   return old;
 }
 
 extern "C" int ctclip_attn_set_fwd_qb(int qb) {
-  if (g_fwd_qb < 0) { const char* e = getenv("CTCLIP_ATTN_FWD_QB"); g_fwd_qb = e ? atoi(e) : 3; }
   const int old = g_fwd_qb;
   if (qb >= 1 && qb <= 3) g_fwd_qb = qb;
   return old;

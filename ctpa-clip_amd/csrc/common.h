@@ -138,16 +138,6 @@ __device__ __forceinline__ float erf_fast(float x) {
   const float r = fmaf(-y, __expf(-a * a), 1.0f);
   return copysignf(r, x);
 }
-#ifdef CTCLIP_DIAG_CHEAP_GELU
-// diagnostic A/B build only (tools/gelu_cost_ab.py): WRONG activations, to time what the erf costs
-// inside the GEGLU / GELU GEMM epilogues
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x; }
-__device__ __forceinline__ float gelu_erf_grad(float x) { return 0.5f + 0.1f * x; }
-__device__ __forceinline__ void gelu_erf_and_grad(float x, float& gelu, float& dgelu) {
-  gelu = gelu_erf(x);
-  dgelu = gelu_erf_grad(x);
-}
-#else
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752f)); }
 // GELU and its derivative together (the GEGLU backward needs both): one erf, and the pdf's
 // exp(-x^2 / 2) is the erf's own exp(-a^2), a = |x| / sqrt 2.  gelu bit-identical to gelu_erf.
@@ -171,7 +161,6 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {   // one exp (gelu_erf
   gelu_erf_and_grad(x, ge, dge);
   return dge;
 }
-#endif
 
 __device__ __forceinline__ float warp_sum(float v) {
 #pragma unroll

@@ -43,13 +43,13 @@ struct P {
   int64_t sA, sB, sC, sC2, sR;
   int n2;        // act 5: columns of C2 (the per-head l2norm of C)
   int64_t kper;
-  int debug;     // diagnostic knob (CTCLIP_G256_DEBUG): 1 = skip the epilogue, 2 = skip the main loop
-  int group_gx;  // grouped (8-row) tile walk when the N tile count >= this (CTCLIP_GEMM_GROUP_GX, default 8)
-  int group_gm;  // rows per group of that walk (CTCLIP_GEMM_GROUP_GM; 0 = 8)
+  int debug;     // always 0 (1 = skip the epilogue, 2 = skip the main loop: a retired diagnostic)
+  int group_gx;  // grouped (8-row) tile walk when the N tile count >= this (8; ctclip_gemm_ln: never)
+  int group_gm;  // rows per group of that walk (0 = 8)
   int stagger;   // start delay (s_sleep units of 64 cycles) for the second co-resident workgroup
   int gz;        // batch * split_k (8-phase tile count = ceil(N/256) * ceil(M/256) * gz)
   int persist;   // 8-phase: persistent workgroups (one per CU) walking the tile sequence
-  int pre1;      // 8-phase TR: the next tile's whole K-step 1 staged before the epilogue (CTCLIP_GEMM_PRE1)
+  int pre1;      // 8-phase TR: the next tile's whole K-step 1 staged before the epilogue (the persistent walk)
   // LayerNorm epilogues (EP -6 forward, -7 backward; ctclip_gemm_ln)
   const float* ln_gamma; const float* ln_beta; float ln_eps;
   u16* ln_y; int64_t ln_ldy;         // -6: LN output (bf16)
@@ -644,36 +644,8 @@ __device__ __forceinline__ u32x4 pair_swap_h(const float* x4, const float* y4) {
   return make_uint4(r0[0], r1[0], r0[1], r1[1]);
 }
 
-// value of lane ^ 16 / lane ^ 32 through v_permlane16_swap / v_permlane32_swap (VALU) instead of
-// ds_bpermute (the LDS crossbar, ~100+ cycles each in the argmax / l2norm epilogues).  Swapping x
-// with itself leaves (even rows / low half in [0], odd rows / high half in [1]) exchanged copies.
-__device__ __forceinline__ unsigned xor16_u(unsigned x, int lane) {
-  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-  return (lane & 16) ? r[0] : r[1];
-}
-__device__ __forceinline__ unsigned xor32_u(unsigned x, int lane) {
-  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return (lane & 32) ? r[0] : r[1];
-}
-template <int O> __device__ __forceinline__ float xorf(float x, int lane) {
-  return __uint_as_float(O == 16 ? xor16_u(__float_as_uint(x), lane) : xor32_u(__float_as_uint(x), lane));
-}
-template <int O> __device__ __forceinline__ int xori(int x, int lane) {
-  return (int)(O == 16 ? xor16_u((unsigned)x, lane) : xor32_u((unsigned)x, lane));
-}
-
-// 16-B epilogue store; CTCLIP_EPI_SC1 (A/B build): write-through sc1, which drops the line from
-// the XCD's L2 instead of keeping it (MI355X_MICROARCH.md, store flavours), so the output stream
-// does not evict the operand panels that the XCD's other tiles re-read
-__device__ __forceinline__ void st16(void* p, u32x4 d) {
-#ifdef CTCLIP_EPI_SC1
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-  const v4u dv = {d.x, d.y, d.z, d.w};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(dv) : "memory");
-#else
-  *(u32x4*)p = d;
-#endif
-}
+// 16-B epilogue store
+__device__ __forceinline__ void st16(void* p, u32x4 d) { *(u32x4*)p = d; }
 
 // 16-B store that drops its line from the XCD's L2 (sc1; MI355X_MICROARCH.md, store flavours)
 __device__ __forceinline__ void st16_sc1(void* p, u32x4 d) {
@@ -735,12 +707,8 @@ __device__ __forceinline__ void store_blk_bf16_lds(char* scr, u16* C, int64_t ld
 // MODE (compile time, so each variant's row loop stays small enough to unroll fully and the
 // accumulator never leaves registers): 0 = general (bias / residual / GELU / f32 or bf16 /
 // accumulate / shadow), 2 = GEGLU, 3 = argmax, 4 = GEGLU backward, 5 = split-K slab.
-#ifndef CTCLIP_GEMM_PERMLANE
-#define CTCLIP_GEMM_PERMLANE 0
-#endif
-// A/B build switch of the xor16 / xor32 exchanges: permlane swaps measured 2 % slower than
-// ds_bpermute on the VQ argmax GEMM (1.193 vs 1.171-1.176 ms, profiles/r02aw_*), so off
-constexpr bool GEMM_PERMLANE = CTCLIP_GEMM_PERMLANE;
+// (the xor16 / xor32 exchanges below are ds_bpermute shuffles: permlane swaps measured 2 % slower on
+// the VQ argmax GEMM, 1.193 vs 1.171-1.176 ms, profiles/r02aw_*)
 
 template <int MODE, bool LDS = false, bool H16 = false, bool X3 = false>
 __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int wr, int wc, int lane, int64_t m0,
@@ -798,14 +766,9 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
         bi = take ? oi : bi;
         best = take ? ob : best;
       };
-      if (GEMM_PERMLANE) {
-        { const float ob = xorf<16>(best, lane), os = xorf<16>(second, lane); merge(ob, os, xori<16>(bi, lane)); }
-        { const float ob = xorf<32>(best, lane), os = xorf<32>(second, lane); merge(ob, os, xori<32>(bi, lane)); }
-      } else {
 #pragma unroll
-        for (int o = 16; o <= 32; o <<= 1)
-          merge(__shfl_xor(best, o, 64), __shfl_xor(second, o, 64), __shfl_xor(bi, o, 64));
-      }
+      for (int o = 16; o <= 32; o <<= 1)
+        merge(__shfl_xor(best, o, 64), __shfl_xor(second, o, 64), __shfl_xor(bi, o, 64));
       if (g == 0 && rok && wcol0 < p.N) {
         float2* out = (float2*)p.C + bidx * p.sC;
         out[gm * p.ldc + (wcol0 >> 6)] = make_float2(best, __int_as_float((int)(wcol0 + bi)));
@@ -856,13 +819,8 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
           float ss = 0.f;
 #pragma unroll
           for (int e = 0; e < 8; ++e) ss += c8[e] * c8[e];
-          if (GEMM_PERMLANE) {
-            ss += xorf<32>(ss, lane);
-            ss += xorf<16>(ss, lane);
-          } else {
-            ss += __shfl_xor(ss, 32, 64);
-            ss += __shfl_xor(ss, 16, 64);
-          }
+          ss += __shfl_xor(ss, 32, 64);
+          ss += __shfl_xor(ss, 16, 64);
           const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
           float o8[8];
 #pragma unroll
@@ -1043,89 +1001,15 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
   }
 }
 
-// GEGLU backward fused into dg = dy . W2 (TR layout): the accumulator is dg over g-space
-// columns; block pair (0,1) is 32-group t0 = wcol0 / 32, pair (2,3) group t0 + 1.  dg is
-// rounded to bf16 (as the stand-alone geglu_bwd reads it) and permlane-paired so every lane
-// owns 8 consecutive g-columns: one 16-B load of h's x part, one of its gate part, one 16-B
-// store each of dh.  The next row block's h loads are issued before this block's math.
-#ifndef GEGLU_BWD_LA
-#define GEGLU_BWD_LA 1
-#endif
-__device__ __forceinline__ void epilogue_geglu_bwd(const P& p, f32x4 (&acc)[8][4], int wr, int wc, int lane,
-                                                   int64_t m0, int64_t n0, int bidx) {
-  const int m = lane & 15, g = lane >> 4;
-  const int64_t wrow0 = m0 + wr * 128, wcol0 = n0 + wc * 64, t0 = wcol0 >> 5;
-  const int co = pair_coff(g);
-  const u16* hb = (const u16*)p.R + bidx * p.sR;
-  u16* db = (u16*)p.C + bidx * p.sC;
-  constexpr int LA = GEGLU_BWD_LA;   // row blocks of h loads in flight ahead of the math
-  u32x4 hx[LA + 1][2], hg[LA + 1][2];
-  auto load = [&](int i, int b) {
-    const int64_t gm = wrow0 + i * 16 + m;
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp) {
-      const int64_t t = t0 + jp;
-      if (gm < p.M && t * 32 < p.N) {
-        const u16* hp = hb + gm * p.ldr + t * 64 + co;
-        hx[b][jp] = *(const u32x4*)hp;
-        hg[b][jp] = *(const u32x4*)(hp + 32);
-      } else {
-        hx[b][jp] = make_uint4(0, 0, 0, 0);
-        hg[b][jp] = make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < LA; ++i) load(i, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int b = i % (LA + 1);
-    if (i + LA < 8) load(i + LA, (i + LA) % (LA + 1));
-    const int64_t gm = wrow0 + i * 16 + m;
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp) {
-      float v0[4], v1[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { v0[r] = acc[i][2 * jp][r] * p.alpha; v1[r] = acc[i][2 * jp + 1][r] * p.alpha; }
-      float d[8], x[8], gt[8], ox[8], og[8];
-      unpack8(pair_swap(v0, v1), d);
-      if (p.h16) {   // h from the fp16 forward (wave-uniform): the derivative form, two multiplies
-        unpack8h(hx[b][jp], x);    // gelu(gate)
-        unpack8h(hg[b][jp], gt);   // x gelu'(gate)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          ox[k] = d[k] * x[k];
-          og[k] = d[k] * gt[k];
-        }
-      } else {
-        unpack8(hx[b][jp], x);
-        unpack8(hg[b][jp], gt);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          float ge, dge;
-          gelu_erf_and_grad(gt[k], ge, dge);
-          ox[k] = d[k] * ge;
-          og[k] = d[k] * x[k] * dge;
-        }
-      }
-      const int64_t t = t0 + jp;
-      if (gm < p.M && t * 32 < p.N) {
-        u16* dp = db + gm * p.ldc + t * 64 + co;
-        st16(dp, pack8(ox));
-        st16(dp + 32, pack8(og));
-      }
-    }
-  }
-}
-
-// The same epilogue with row-contiguous global accesses (EP 14, CTCLIP_GEGLU_BWD_RELAY, default
-// on).  Above, a lane of the transposed layout owns one row (lane & 15), so every 16-B load of h and
-// store of dh touches 16 rows x 64 B: the access shape store_blk_bf16_lds was written for.  Here a
-// wave's 64 g-columns are taken as what they are in memory, 256 contiguous bytes of an h / dh row
+// GEGLU backward fused into dg = dy . W2 (TR layout, EP 14): the accumulator is dg over g-space
+// columns; block pair (0,1) is 32-group t0 = wcol0 / 32, pair (2,3) group t0 + 1.  dg is rounded to
+// bf16 (as the stand-alone geglu_bwd reads it) and permlane-paired so every lane owns 8 consecutive
+// g-columns.  A lane of the transposed layout owns one row (lane & 15), so a 16-B load of h or store of
+// dh straight from it would touch 16 rows x 64 B: the access shape store_blk_bf16_lds was written for.
+// Instead a wave's 64 g-columns are taken as what they are in memory, 256 contiguous bytes of an h / dh row
 // ([x | gate] of 32-groups t0 and t0 + 1): a 16-row block is read with 16 lanes per row, 4 whole
 // rows per instruction, staged in the wave's 4 KB LDS strip, read back in the transposed layout,
-// overwritten in place with dh and stored row-major again.  Element for element the arithmetic is
-// that of epilogue_geglu_bwd (dg rounded to bf16, the same multiplies in the same order).
+// overwritten in place with dh and stored row-major again.
 // Strip image: row r (of 16) at r * 256 B, its 16-B chunk c at chunk slot c ^ r.  The row-major
 // side touches the 16 slots of a row per 16 lanes, the transposed side (rows 0..15 at one logical
 // chunk) 16 different slots: both conflict-free for the b128 lane groups (MI355X_MICROARCH.md, LDS).
@@ -1569,20 +1453,6 @@ __device__ __forceinline__ Tile tile_at(const P& p, int lin, int gx, int gy, int
   return t;
 }
 
-#ifdef CTCLIP_GEMM_STAMPS
-// diagnostic build only (tools/gemm_stamps.py): per (workgroup, tile) s_memtime stamps of thread 0
-// (0 tile start, 1 after the first K-tile, 2 after the second, 3 after the last MFMA + barrier,
-// 4 after the epilogue's stores are issued) and the tile start in s_memrealtime (5, chip-wide)
-__device__ unsigned long long g_stamps[256][32][6];
-#define STAMP(k, v)                                                                        \
-  do {                                                                                     \
-    const unsigned long long t_ = (v);                                                     \
-    if (threadIdx.x == 0 && tcount < 32) g_stamps[blockIdx.x][tcount][k] = t_;             \
-  } while (0)
-#else
-#define STAMP(k, v) do { } while (0)
-#endif
-
 template <bool AK, bool BKC, int EP, bool H16 = false, bool X3 = false>
 __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
   using namespace p8;
@@ -1691,8 +1561,6 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
   stage(A0, 1); stage(B0, 1);
   wait_ahead(T.nk > 1);
 
-  int tcount = 0;
-  (void)tcount;
   // TR epilogues without the LDS relay (EP 10 / 12 use O's A1 / B1 halves as scratch) leave buffer O
   // idle, so with p.pre1 the next tile's K-step 1 is staged whole before the epilogue: its A1 / B1
   // halves get the epilogue's duration to land instead of the three MFMA phases of K-step 0 (the
@@ -1705,16 +1573,13 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
   // end to end within noise (r04s_pre1_ab_bench.log).  Skipping the re-issue costs the NT plain /
   // GEGLU / l2norm kernels 4-18 spilled VGPRs (FF1 +3 %, Q / KV +7 %), and re-issuing instead
   // gains nothing, so those keep the in-loop staging.
-  constexpr bool PRE_OK = TR && (EP == 3 || EP == 4 || EP == 14 || (EP == 0 && !BKC));
+  constexpr bool PRE_OK = TR && (EP == 3 || EP == 14 || (EP == 0 && !BKC));
   bool pre = false;
   while (true) {
     const int nk = T.nk;
-    STAMP(0, __builtin_amdgcn_s_memtime());
-    STAMP(5, __builtin_amdgcn_s_memrealtime());
     bar();
     if (wr == 1) bar();   // the stagger: waves 4-7 run one barrier behind
     for (int i = 0; 2 * i < nk; ++i) {
-      if (i == 1) STAMP(2, __builtin_amdgcn_s_memtime());
       const int te = 2 * i, to = 2 * i + 1;
       // K-step 1's second halves already staged before the epilogue: not re-issued here (step index
       // nk = no load, the bound check stage_of makes anyway)
@@ -1746,7 +1611,6 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
     }
     if (wr == 0) bar();   // balance the stagger barrier
     __syncthreads();      // every wave's last fragment reads done before LDS is refilled / reused
-    STAMP(3, __builtin_amdgcn_s_memtime());
     lin += lstride;
     const bool more = lin < ntiles;
     if (more) {
@@ -1765,8 +1629,6 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
         for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
     } else if constexpr (EP == 2 || EP == 12) {
       epilogue_t<2, EP == 12, H16, X3>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
-    } else if constexpr (EP == 4) {
-      epilogue_geglu_bwd(p, acc, wr, wc, lane, T.m0, T.n0, T.bidx);
     } else if constexpr (EP == 14) {
       epilogue_geglu_bwd_rows(p, acc, wr, wc, lane, T.m0, T.n0, T.bidx, smem + 2 * TILEB + wu * GB_STRIP);
     } else if constexpr (EP == 0 || EP == 10) {
@@ -1785,8 +1647,6 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
       // staging in buffer O and beyond (the next tile's tile 0 is landing in E)
       epilogue<EP == -2 || EP == -3 || EP == -5 ? EP : -1>(p, acc, smem + TILEB, w, wr, wc, lane, T.m0, T.n0, T.split, T.bidx);
     }
-    STAMP(4, __builtin_amdgcn_s_memtime());
-    ++tcount;
     if (!more) break;
     T = tile_at<X3>(p, lin, gx, gy, ntiles);
 #pragma unroll
@@ -1815,19 +1675,11 @@ int launch8(const P& p, int batch, hipStream_t st) {
     attr = true;
   }
   const int64_t ntiles = cdiv(p.N, p8::BNN) * cdiv(p.M, p8::BM) * (int64_t)p.gz;
-  static bool cap_env = false;   // CTCLIP_GEMM_GRID_CAP (A/B): persistent grid below one per CU
-  if (!cap_env) {
-    const char* e = getenv("CTCLIP_GEMM_GRID_CAP");
-    if (e && g_grid_cap == 0) g_grid_cap = atoi(e);
-    cap_env = true;
-  }
-  static int pre1 = -1;   // CTCLIP_GEMM_PRE1=0: K-step 1's A1 / B1 halves staged inside the loop (A/B)
-  if (pre1 < 0) { const char* e = getenv("CTCLIP_GEMM_PRE1"); pre1 = e ? atoi(e) != 0 : 1; }
   if (p.persist) {
     const int64_t cap = g_grid_cap > 0 && g_grid_cap < 256 ? g_grid_cap : 256;
     dim3 grid((unsigned)(ntiles < cap ? ntiles : cap));
     P q = p;
-    q.pre1 = pre1;
+    q.pre1 = 1;
     hipLaunchKernelGGL((gemm8p_kernel<AK, BKC, EP, H16, X3>), grid, dim3(p8::NTH), smem, st, q);
   } else {
     dim3 grid(cdiv(p.N, p8::BNN), cdiv(p.M, p8::BM), batch * p.split_k);
@@ -1861,40 +1713,24 @@ int launch_any(const P& p, bool ak, bool bk, int batch, hipStream_t st) {
 }
 
 // kernel variant: 8 = 8-phase 256 x 256 x 64 (default), 1 = 128 x 256 x 32 (2 WG/CU),
-// 2 = 256 x 256 x 32 4-slot ring.  CTCLIP_GEMM_VARIANT or ctclip_gemm_set_variant() select it.
-static int g_variant = -1;
+// 2 = 256 x 256 x 32 4-slot ring.  ctclip_gemm_set_variant() selects it.
+static int g_variant = 8;
 static int g_stagger8 = -1;   // 8-phase start stagger (units of s_sleep(32)); -1 = default
-static int g_persist = -1;    // 8-phase persistent tile loop (CTCLIP_GEMM_PERSIST, default on)
-static int g_epi_lds = -1;    // transposed bf16 / GEGLU epilogues through LDS (CTCLIP_EPI_LDS)
-int variant() {
-  if (g_variant < 0) {
-    const char* e = getenv("CTCLIP_GEMM_VARIANT");
-    g_variant = e ? atoi(e) : 8;
-    if (g_variant != 1 && g_variant != 2) g_variant = 8;
-  }
-  return g_variant;
-}
+static int g_persist = 1;     // 8-phase persistent tile loop (ctclip_gemm_set_persist)
+static int g_epi_lds = 0;     // transposed bf16 / GEGLU epilogues through LDS (ctclip_gemm_set_epi_lds)
+int variant() { return g_variant; }
 int tile_rows() { return variant() == 2 ? 2 : 1; }
 
 // epilogue kind, one kernel instantiation each (so the accumulator registers never share a
 // kernel with another epilogue's live ranges): -1 = LDS-staged rows (f32 / residual / argmax /
 // split-K slabs), 0 = transposed bf16, 2 = transposed GEGLU, 4 = transposed GEGLU backward,
-// 10 / 12 = 0 / 2 with their bf16 stores re-laid through LDS (store_blk_bf16_lds), 14 = 4 with its h
-// loads and dh stores row-contiguous through LDS (epilogue_geglu_bwd_rows)
+// 10 / 12 = 0 / 2 with their bf16 stores re-laid through LDS (store_blk_bf16_lds), 14 = the GEGLU
+// backward, its h loads and dh stores row-contiguous through LDS (epilogue_geglu_bwd_rows)
 template <bool AK, bool BKC>
 int launch8_ep(const P& p, int batch, hipStream_t st) {
-  if (p.act == 4) {
-    // 14: h loads and dh stores row-contiguous through a wave-private LDS strip; CTCLIP_GEGLU_BWD_RELAY=0:
-    // the lane-per-row epilogue (A/B)
-    static int gb_rows = -1;
-    if (gb_rows < 0) { const char* e = getenv("CTCLIP_GEGLU_BWD_RELAY"); gb_rows = e ? atoi(e) != 0 : 1; }
-    return gb_rows ? launch8<AK, BKC, 14>(p, batch, st) : launch8<AK, BKC, 4>(p, batch, st);
-  }
+  if (p.act == 4) return launch8<AK, BKC, 14>(p, batch, st);
   if (p.act == 5) return launch8<AK, BKC, 6>(p, batch, st);
-  // CTCLIP_GEMM_TR_F32=1 (A/B): f32 / residual outputs through the transposed (LDS-free) epilogue too
-  static int tr_f32 = -1;
-  if (tr_f32 < 0) { const char* e = getenv("CTCLIP_GEMM_TR_F32"); tr_f32 = e ? atoi(e) != 0 : 0; }
-  const bool tr = (tr_f32 || (!p.c_f32 && !p.R)) && p.split_k <= 1 && p.act != 3;
+  const bool tr = !p.c_f32 && !p.R && p.split_k <= 1 && p.act != 3;
   if (!tr) {
     // the argmax through the transposed (LDS-free) epilogue: VQ distance GEMM 1.73 -> 1.56 ms (r02);
     // CTCLIP_GEMM_ARGMAX_TR=0: the LDS-staged one (A/B)
@@ -1966,37 +1802,17 @@ int ctclip_gemm256(const ctclip_gemm_args* a, int split, int batch, void* stream
   p.C4 = (u16*)a->C4; p.ldc4 = a->ldc4;
   const int kstep = (variant() == 8 || a->act == 4 || a->act == 5) ? p8::BKK : BK;
   p.kper = (a->K / kstep + split - 1) / split * kstep;
-  static int dbg = -1, stag = 0;
-  if (dbg < 0) {
-    const char* e = getenv("CTCLIP_G256_DEBUG");
-    dbg = e ? atoi(e) : 0;
-    const char* s = getenv("CTCLIP_G256_STAGGER");
-    stag = s ? atoi(s) : 0;
-  }
-  p.debug = dbg;
-  if (g_persist < 0) {
-    const char* e = getenv("CTCLIP_GEMM_PERSIST");
-    g_persist = e ? (atoi(e) != 0) : 1;
-  }
   p.gz = batch * split;
   p.persist = g_persist;
-  if (g_epi_lds < 0) {
-    const char* e = getenv("CTCLIP_EPI_LDS");
-    g_epi_lds = e ? std::min(3, std::max(0, atoi(e))) : 0;
-  }
   p.epi_lds = g_epi_lds;
+  p.group_gx = 8;   // r02: FF1 (11 tiles) -2%, VQ (32) -17%; N <= 6 tiles: neutral to +4% (not grouped)
+  p.group_gm = 8;
   // 8-phase default: stagger only the GEGLU GEMM, whose epilogue (h + g stores + erf) is long
   // enough that desynchronised CUs pay off (r01 sweep: 0.52 -> 0.48 ms at B = 8; neutral to
   // slightly negative on the plain / residual epilogues)
-  static int ggx = -1;
-  if (ggx < 0) { const char* e = getenv("CTCLIP_GEMM_GROUP_GX"); ggx = e ? atoi(e) : 8; }   // r02: FF1 (11 tiles) -2%, VQ (32) -17%; N <= 6 tiles: neutral to +4% (not grouped)
-  p.group_gx = ggx;
-  static int ggm = -1;
-  if (ggm < 0) { const char* e = getenv("CTCLIP_GEMM_GROUP_GM"); ggm = e ? atoi(e) : 8; }
-  p.group_gm = ggm;
   // (round 4 sweep, profiles/r04a_stagger.log, interleaved rounds: no start stagger is best for the
   // GEGLU GEMM now -- 0.4229 vs 0.4289 ms at the old default 4; the GEGLU backward gains ~1.5 % at 8)
-  p.stagger = variant() == 8 ? (g_stagger8 >= 0 ? g_stagger8 : (a->act == 4 ? 8 : 0)) : (tile_rows() == 1 ? stag : 0);
+  p.stagger = variant() == 8 ? (g_stagger8 >= 0 ? g_stagger8 : (a->act == 4 ? 8 : 0)) : 0;
   hipStream_t st = (hipStream_t)stream;
   if (a->ab_f16) {
     if (!a->a_kcontig || !a->b_kcontig) return CT_EINVAL;
@@ -2114,10 +1930,6 @@ extern "C" int ctclip_gemm_qkv_lnfold2(const ctclip_gemm_args* a, const float* m
   p.n2 = a->n2;
   p.kper = a->K;
   p.gz = 1;
-  if (g_persist < 0) {
-    const char* e = getenv("CTCLIP_GEMM_PERSIST");
-    g_persist = e ? (atoi(e) != 0) : 1;
-  }
   p.persist = g_persist;
   p.group_gx = 8;
   p.ln_mean = (float*)mean;
@@ -2159,10 +1971,6 @@ extern "C" int ctclip_gemm_lnfold_bwd(const ctclip_gemm_args* a, const void* X, 
   p.alpha = a->alpha; p.split_k = 1;
   p.kper = a->K;
   p.gz = 1;
-  if (g_persist < 0) {
-    const char* e = getenv("CTCLIP_GEMM_PERSIST");
-    g_persist = e ? (atoi(e) != 0) : 1;
-  }
   p.persist = g_persist;
   p.group_gx = 8;
   p.ln_x = (const u16*)X;
@@ -2209,15 +2017,3 @@ extern "C" int ctclip_gemm_set_variant(int v) {
   if (v == 1 || v == 2 || v == 8) g256::g_variant = v;
   return old;
 }
-
-#ifdef CTCLIP_GEMM_STAMPS
-// diagnostic: copy the stamp buffer (256 x 32 x 6 u64) to host memory (and clear it)
-extern "C" int ctclip_gemm_stamps(void* host, int clear) {
-  hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g256::g_stamps), sizeof(g256::g_stamps), 0, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && clear) {
-    static unsigned long long zero[256 * 32 * 6];
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g256::g_stamps), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-  }
-  return (int)e;
-}
-#endif

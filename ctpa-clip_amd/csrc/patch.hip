@@ -317,8 +317,7 @@ __global__ __launch_bounds__(256) void patch_ln_strip20_kernel(const void* __res
 }
 
 bool s_strip_attr = false;
-// A/B switch of the strip20 kernel's XCD-aware block order (CTCLIP_PATCH_XCD=0: dispatch order)
-int s_patch_remap = [] { const char* e = getenv("CTCLIP_PATCH_XCD"); return e ? atoi(e) != 0 : 1; }();
+constexpr int s_patch_remap = 1;   // the strip20 kernel's XCD-aware block order (0: dispatch order)
 bool s_strip20_attr = false;
 
 // Given G = dy^T . xhat  [N][K] (f32) and colsum(dy) cs[N], produce the grads of the folded

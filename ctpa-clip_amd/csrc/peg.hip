@@ -183,12 +183,9 @@ __global__ __launch_bounds__(192) void peg_wgrad_kernel(const u16* __restrict__ 
 // three read in step t, so one barrier per step suffices.
 // W <= 24 (one item per thread); 3 ring slots + weights = 47 KB -> 3 workgroups per CU, so the
 // base grid (8 x 12 x 8 = 768 workgroups) is resident in one round
-#ifndef CTCLIP_PEG_SEG
-#define CTCLIP_PEG_SEG 3
-#endif
 // SEG w positions per conv thread; TNTH = one (row, segment, chunk) item per thread on the 24-wide
 // grid; PLANE_CH = 16-B chunks a plane (HT + 2 rows x W + 2 columns x 8 chunks) may hold
-constexpr int HT = 2, SEG = CTCLIP_PEG_SEG, SEGW = 6, TNTH = HT * ((24 + SEG - 1) / SEG) * 8, WNTH = 256,
+constexpr int HT = 2, SEG = 3, SEGW = 6, TNTH = HT * ((24 + SEG - 1) / SEG) * 8, WNTH = 256,
               PLANE_CH = 1024, NSLOT = 3;
 template <int NT> constexpr int nld() { return (PLANE_CH + NT - 1) / NT; }   // plane loads per thread
 
@@ -429,9 +426,6 @@ __global__ __launch_bounds__(TNTH) void peg_tile_kernel(const u16* __restrict__ 
 // threads per CU, the base grid (8 x 6 x 16 = 768 workgroups) resident in one round.
 // Outputs: f32, bf16 shadow, optional f16 copy (a 16-bit MFMA A operand) and optional (mean, M2)
 // per 32-channel group (D / 32 groups, ctclip_ln_stats_merge).
-#ifndef CTCLIP_PEGX_WAVES
-#define CTCLIP_PEGX_WAVES 1   // launch-bounds occupancy floor (waves per SIMD): 1 = the compiler's choice
-#endif
 constexpr int XC = 32;             // channels per workgroup
 constexpr int XHT = 4;             // output rows per workgroup
 constexpr int XNT = 256;           // threads: XHT x ceil(W / SEG) x 8 chunks of 4 channels
@@ -473,7 +467,7 @@ __device__ __forceinline__ void xplane_store(char* dst, int W, const u32x4 (&reg
 // keeps its direction and its one plane of lead.  Columns mirror (x[w + 1 - kw] instead of
 // x[w - 1 + kw]); rows use the transposed row offsets (Taps<MD, 1>).  No bias, no statistics.
 template <int GK = 0, int MD = 0, int TR = 0>
-__global__ __launch_bounds__(XNT, CTCLIP_PEGX_WAVES) void peg_fwd32_kernel(const float* __restrict__ xin, int D,
+__global__ __launch_bounds__(XNT, 1) void peg_fwd32_kernel(const float* __restrict__ xin, int D,
                                                         const float* __restrict__ w, const float* __restrict__ bias,
                                                         Geo g, float* __restrict__ out, u16* __restrict__ outb,
                                                         u16* __restrict__ outh, float* __restrict__ stats,
@@ -837,13 +831,9 @@ bool fixed24(const Geo& g) {
   return on && g.T == 24 && g.H == 24 && g.W == 24 && (g.mode == 0 || g.mode == 1);
 }
 
-// mode 1 on the 24^3 cube through the canonical walk (MD 2); CTCLIP_PEG_CANON1=0 or
-// ctclip_peg_set_canon1(0): the view walk (A/B)
-int g_canon1 = -1;
-bool canon1() {
-  if (g_canon1 < 0) { const char* e = getenv("CTCLIP_PEG_CANON1"); g_canon1 = e ? atoi(e) != 0 : 1; }
-  return g_canon1 != 0;
-}
+// mode 1 on the 24^3 cube through the canonical walk (MD 2); ctclip_peg_set_canon1(0): the view walk (A/B)
+int g_canon1 = 1;
+bool canon1() { return g_canon1 != 0; }
 
 template <int TR>
 void launch_tile(dim3 grid, size_t smem, hipStream_t st, const u16* x, int D, const float* w, const float* bias,

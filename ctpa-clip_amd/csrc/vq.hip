@@ -17,11 +17,6 @@
 #include "common.h"
 #include "../../include/ctclip_hip.h"
 
-// diagnostic build only (timing the full-group re-score; wrong indices): treat every group as single
-#ifndef CTCLIP_VQ_DIAG_NOFULL
-#define CTCLIP_VQ_DIAG_NOFULL 0
-#endif
-
 namespace {
 
 constexpr int VQ_SB = 4;   // single-code candidates re-scored together
@@ -184,7 +179,7 @@ __global__ __launch_bounds__(256) void vq_select_kernel(const float2* __restrict
     auto chunk = [&](int t0, float2 c, float c2) {
       const int t = t0 + lane;
       const bool take = t < ntiles && c.x >= thr;
-      const bool full = !CTCLIP_VQ_DIAG_NOFULL && take && cand2 && c2 >= thr;
+      const bool full = take && cand2 && c2 >= thr;
       unsigned long long gmask = __ballot(full);
       unsigned long long smask = __ballot(take) & ~gmask;
       while (gmask) {

@@ -10,7 +10,6 @@ compatibility; the pooler output is unused by CT-CLIP and is not computed.
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 
 import torch
@@ -19,11 +18,6 @@ from torch import nn
 from . import dist_sync
 from . import functional as Fn
 from . import streams
-
-
-# diagnostic only (A/B of what the dropout sites cost): CTCLIP_BERT_NODROP=1 runs train mode without
-# dropout, which is NOT the reference's work
-_NO_DROP = os.environ.get('CTCLIP_BERT_NODROP', '0') != '0'
 
 
 @dataclass
@@ -205,8 +199,8 @@ class BertModel(nn.Module):
         # train-mode dropout (HF BertEmbeddings / BertSelfAttention / BertSelfOutput / BertOutput):
         # one 64-bit seed per (forward call, layer, site); the masks are hashes of it (no host RNG state
         # on the step path, the backward regenerates them)
-        ph = float(c.hidden_dropout_prob) if self.training and not _NO_DROP else 0.0
-        pa = float(c.attention_probs_dropout_prob) if self.training and not _NO_DROP else 0.0
+        ph = float(c.hidden_dropout_prob) if self.training else 0.0
+        pa = float(c.attention_probs_dropout_prob) if self.training else 0.0
         self._drop_calls = getattr(self, '_drop_calls', 0) + 1
         base = (torch.initial_seed() * 0x2545F4914F6CDD1D + self._drop_calls * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
 
@@ -229,8 +223,7 @@ class BertModel(nn.Module):
                 a.output.LayerNorm.weight, a.output.LayerNorm.bias, lyr.intermediate.dense.weight,
                 lyr.intermediate.dense.bias, lyr.output.dense.weight, lyr.output.dense.bias,
                 lyr.output.LayerNorm.weight, lyr.output.LayerNorm.bias,
-                (ph, pa, seed(li + 1, 0), seed(li + 1, 1), seed(li + 1, 2)),
-                li >= len(self.encoder.layer) - Fn._TEXT_SPLIT_LAYERS)
+                (ph, pa, seed(li + 1, 0), seed(li + 1, 1), seed(li + 1, 2)))
             if li in lows and li > 0:
                 dist_sync.mark_ready(xf, f'text_{li}')
         return (xf.view(B, L, c.hidden_size), None)

@@ -263,16 +263,7 @@ def bf(W):
 # The text tower's forward GEMMs read each weight as W = hi + lo (two bf16 images, ~16 mantissa
 # bits; gemm.hip walks K twice into one f32 accumulator): the bf16 rounding of BERT-base's weights
 # is what put its latents 1.4e-3 off the f32 reference (tools/bert_precision.py: 6e-4 without
-# it).  CTCLIP_TEXT_SPLIT=0 restores single bf16 weights (A/B switch).
-_TEXT_SPLIT = os.environ.get('CTCLIP_TEXT_SPLIT', '1') != '0'
-# hi / lo split weights on the top CTCLIP_TEXT_SPLIT_LAYERS BERT layers only (default: all 12)
-_TEXT_SPLIT_LAYERS = int(os.environ.get('CTCLIP_TEXT_SPLIT_LAYERS', '1000'))
-# BERT hidden dropout folded into the split-K combine (forward) and the LayerNorm backward, the
-# GELU backward into the dX GEMM (act 6), the dense bias gradients into the LayerNorm backward's
-# partials; CTCLIP_BERT_FUSE=0 restores the stand-alone dropout / gelu_bwd / colsum kernels (A/B)
-_BERT_FUSE = os.environ.get('CTCLIP_BERT_FUSE', '1') != '0'
-# A/B only: the FeedForward's K = 2,816 dX GEMM (a plain bf16 output) on hipBLASLt via torch.matmul
-_DXN2_BLAS = os.environ.get('CTCLIP_DXN2_BLAS', '0') != '0'
+# it).  BertLayerFn's split= argument selects it per layer.
 
 
 def bf_split(W):
@@ -315,23 +306,12 @@ def _adjacent(ts, arena_of):
 # call, weights once per optimizer update.  The backward stays bf16 on the same saved bf16
 # activations and weights.  SURVEY 8(c): compared to the build's own bf16 path, tolerance per test.
 _FP8 = {'on': False}
-_L2N_FUSED = os.environ.get('CTCLIP_L2N_FUSED', '1') != '0'   # A/B switch of the act-5 projections
 # The attention's pre-norm LayerNorm folded into ONE Q | K | V projection over the PEG output
 # (gemm256.hip EP 8, ctclip_gemm_qkv_lnfold): PEG leaves the LayerNorm statistics, the Q columns
 # compute LN(x) Wq^T = rstd (x (gamma o Wq)^T - mean Wq gamma), so neither the LayerNorm kernel
 # nor its output exists; the Q weight gradient uses the same fold (ctclip_lnfold_wgrad).
 # CTCLIP_LN1_FOLD=0: the LayerNorm kernel and the two projections (A/B switch).
 _LN1_FOLD = os.environ.get('CTCLIP_LN1_FOLD', '1') != '0'
-# the FeedForward weight gradients' split-K slabs reduced straight into the unpacked .grad rows
-# (ctclip_reduce_slabs_rows); CTCLIP_DW_UNPACK_FUSED=0: slab reduction + unpack_rows (A/B)
-_DW_UNPACK_FUSED = os.environ.get('CTCLIP_DW_UNPACK_FUSED', '1') != '0'
-# the training VQ's EMA statistics accumulated in code-sorted order (kernels.vq_ema_accum with a work
-# buffer: ~10x fewer int64 atomics than the token-order kernel, same sums bit for bit);
-# CTCLIP_VQ_EMA_SORTED=0: token order (A/B)
-_EMA_SORTED = os.environ.get('CTCLIP_VQ_EMA_SORTED', '1') != '0'
-# fold backward: the q and k l2norm backwards as one pass (ctclip_l2norm_qk_bwd_fold); 0 = two (A/B)
-_QK_BWD_MERGED = os.environ.get('CTCLIP_QK_BWD_MERGED', '1') != '0'
-_QKV_WGRAD = os.environ.get('CTCLIP_QKV_WGRAD', '1') != '0'   # A/B switch of BERT's merged q/k/v wgrad
 # PEG forward taps from the f32 residual stream instead of its bf16 shadow (ctclip_peg_fwd_x32, round 5:
 # the shadow's rounding was ~22 % of the bf16 tower's squared pre-VQ error, tools/vit_precision.py);
 # CTCLIP_PEG_X32=0: the bf16-tap kernel (A/B)
@@ -355,10 +335,6 @@ def set_vit_f16(on):
     old = _VIT_F16['on']
     _VIT_F16['on'] = bool(on)
     return old
-
-
-# image projection forward on the skinny streaming GEMM (ctclip_skinny_gemm); 0 = split-K tile (A/B)
-_SKINNY_PROJ = os.environ.get('CTCLIP_SKINNY_PROJ', '1') != '0'
 
 
 def set_vit_fp8(on):
@@ -653,7 +629,7 @@ class ViTLayerFn(torch.autograd.Function):
             kv = fp8_linear(x1b, Wkv, 'kv', Wkv_b)
             qn = K.l2norm_scale_fwd(q, H, dh, q_scale)
             kn = K.l2norm_scale_fwd(kv[:, :inner], H, dh, k_scale)
-        elif _L2N_FUSED and dh == 32 and inner % 64 == 0:
+        elif dh == 32 and inner % 64 == 0:
             # l2norm(q) * q_scale, l2norm(k) * k_scale fused into the projections' epilogues (act 5)
             qn = torch.empty(xf.shape[0], inner, device=xf.device, dtype=BF16)
             kn = torch.empty(xf.shape[0], inner, device=xf.device, dtype=BF16)
@@ -744,28 +720,17 @@ class ViTLayerFn(torch.autograd.Function):
         # weight gradients reduced from their split-K slabs straight into the unpacked .grad rows
         # (ctclip_reduce_slabs_rows: one pass instead of a slab reduction + unpack_rows)
         if gsink(W2) is not None:
-            if _DW_UNPACK_FUSED:
-                K.matmul_tn(dx3b, g, tag='dw', flops=2.0 * M_ * W2.shape[0] * W2.shape[1],
-                            unpack=(gsink(W2), None, W2.shape[1]))
-            else:
-                K.unpack_rows(K.matmul_tn(dx3b, g, tag='dw', flops=2.0 * M_ * W2.shape[0] * W2.shape[1]), gsink(W2),
-                              cols=W2.shape[1], accumulate=True)
+            K.matmul_tn(dx3b, g, tag='dw', flops=2.0 * M_ * W2.shape[0] * W2.shape[1],
+                        unpack=(gsink(W2), None, W2.shape[1]))
         # dx2 = LN'(dh . W1) + dx3 in one launch where the shape allows (gemm256.hip, EP -7)
         fused = K.matmul_nn_ln_bwd(dh_, W1p, x2b, m2, r2, ff_w, dx3f, dgamma_out=gsink(ff_w),
                                    dbeta_out=gsink(ff_b)) if K.ln_guarded() else None
         if fused is None:
-            if _DXN2_BLAS:    # A/B: hipBLASLt (torch.matmul) for this plain bf16 GEMM, W1 packed K-contiguous
-                dxn2 = torch.matmul(dh_, W1p.t().contiguous().t())
-            else:
-                dxn2 = K.matmul_nn(dh_, W1p)
+            dxn2 = K.matmul_nn(dh_, W1p)
         if gsink(W1) is not None:
             rmap = ff1_rowmap(W1.shape[0] // 2, dev)
-            if _DW_UNPACK_FUSED:
-                K.matmul_tn(dh_, xn2, tag='dw', flops=2.0 * M_ * W1.shape[0] * W1.shape[1],
-                            unpack=(gsink(W1), rmap, W1.shape[1]))
-            else:
-                K.unpack_rows(K.matmul_tn(dh_, xn2, tag='dw', flops=2.0 * M_ * W1.shape[0] * W1.shape[1]), gsink(W1),
-                              rowmap=rmap, accumulate=True)
+            K.matmul_tn(dh_, xn2, tag='dw', flops=2.0 * M_ * W1.shape[0] * W1.shape[1],
+                        unpack=(gsink(W1), rmap, W1.shape[1]))
         if fused is not None:
             dx2f, dx2b = fused
         else:
@@ -798,18 +763,11 @@ class ViTLayerFn(torch.autograd.Function):
                        L=L, H=H, D=dh, nseq=nseq, scale=8.0, seq=seq, bias_u=bias_u if ctx.use_bias else None,
                        dbias_u=du, grid=(geo.Hg, geo.Wg) if ctx.use_bias else (0, 0))
             _bias_grad_ready(ctx, du)
-            if _QK_BWD_MERGED:
-                # both l2norm backwards in one pass over the forward's [q | k] (one wave per row)
-                qk = q.as_strided((M_, 2 * inner), q.stride())
-                _, _, u1, c1, be1 = K.l2norm_qk_bwd_fold(qk, dqkn, q_scale, k_scale, r1, m1, dqkv[:, :2 * inner], cs,
-                                                         x1b.shape[1], ds_q_out=gsink(q_scale),
-                                                         ds_k_out=gsink(k_scale))
-            else:
-                _, _, u1, c1, be1 = K.l2norm_scale_bwd_fold(q, dqkn[:, :inner], H, dh, q_scale, r1, m1,
-                                                            dx2=dqkv[:, :inner], fold_cs=cs, Dm=x1b.shape[1],
-                                                            ds_out=gsink(q_scale))
-                K.l2norm_scale_bwd(kv[:, :inner], dqkn[:, inner:], H, dh, k_scale, dqkv[:, inner:2 * inner],
-                                   ds_out=gsink(k_scale))
+            # both l2norm backwards in one pass over the forward's [q | k] (one wave per row)
+            qk = q.as_strided((M_, 2 * inner), q.stride())
+            _, _, u1, c1, be1 = K.l2norm_qk_bwd_fold(qk, dqkn, q_scale, k_scale, r1, m1, dqkv[:, :2 * inner], cs,
+                                                     x1b.shape[1], ds_q_out=gsink(q_scale),
+                                                     ds_k_out=gsink(k_scale))
             Gqkv = K.matmul_tn(dqkv, x1b, tag='dw')
             gq, gkv = gsink(Wq), gsink(Wkv)      # (frozen projections: scratch sinks)
             K.lnfold_wgrad(Gqkv, u1, norm_g, gq if gq is not None else torch.empty(Wq.shape, device=dev),
@@ -861,7 +819,7 @@ def _fold_shape_ok(geo, dim, Wkv):
     (kernels.l2norm_qk_bwd_fold) is built for exactly 256 q columns, the statistics merge
     (ctclip_ln_stats_merge) for <= 16 64-channel groups."""
     inner = geo.heads * geo.dim_head
-    return (_LN1_FOLD and _L2N_FUSED and geo.dim_head == 32 and inner == 256 and dim % 64 == 0 and dim <= 1024
+    return (_LN1_FOLD and geo.dim_head == 32 and inner == 256 and dim % 64 == 0 and dim <= 1024
             and geo.Wg <= 24 and Wkv.shape[0] == 2 * inner)
 
 
@@ -1036,7 +994,7 @@ class VQPoolFn(torch.autograd.Function):
                     # (the accumulation adds onto what the buffers hold: integer counts in f32 and
                     # fixed-point sums, so statistics held over several calls -- ema_mode 'hold' --
                     # are the bits of one call on all their rows)
-                    work = state.ema_work(C, xn.shape[0], zf.device) if _EMA_SORTED else None
+                    work = state.ema_work(C, xn.shape[0], zf.device)
                     K.vq_ema_accum(idx, xn, bins, esum, work=work)
                 if apply:
                     dist_sync.sum_codebook_stats(bins_g, esum)
@@ -1211,14 +1169,13 @@ class ImageProjFn(torch.autograd.Function):
         if precise_f32() or precise_split():
             # the precise towers' projection in f32: the HBM-streaming skinny GEMM on the f32 weight
             # (ctclip_skinny_sgemm, an f32 fma per product; 604 MB read once), else split-K f32 MFMA
-            out = K.skinny_linear(pooled.detach().contiguous(), W.detach()) if _SKINNY_PROJ else None
+            out = K.skinny_linear(pooled.detach().contiguous(), W.detach())
             return out if out is not None else K.slinear(pooled.detach().contiguous(), W.detach())
         # the HBM-streaming skinny GEMM (csrc/proj.hip): the 302 MB weight read once at ~HBM speed
         # (the generic split-K 128-row MFMA tile ran at 0.85 TB/s at M = 8, round 4)
-        if _SKINNY_PROJ:
-            out = K.skinny_linear(pooled_b, Wb)
-            if out is not None:
-                return out
+        out = K.skinny_linear(pooled_b, Wb)
+        if out is not None:
+            return out
         B, Kd = pooled_b.shape
         N = Wb.shape[0]
         split = max(1, min(512, Kd // 1024))
@@ -1425,7 +1382,7 @@ class BertLayerFn(torch.autograd.Function):
         ph, pa, s_attn, s_out1, s_out2 = drop
         Hd = xf.shape[1]
         dh = Hd // heads
-        split = _TEXT_SPLIT if split is None else (split and _TEXT_SPLIT)
+        split = True if split is None else split
         if split:
             (Wqkv, Wqkv_lo), (Wo_b, Wo_lo), (Wi_b, Wi_lo), (Wout_b, Wout_lo) = (
                 bf_cat_split([Wq, Wk, Wv]), bf_split(Wo), bf_split(Wi), bf_split(Wout))
@@ -1436,19 +1393,15 @@ class BertLayerFn(torch.autograd.Function):
         qkv = K.linear(xb, Wqkv, bias=bqkv, w_lo=Wqkv_lo)
         ctxv, lse = K.attn_fwd(qkv[:, :Hd], qkv[:, Hd:2 * Hd], qkv[:, 2 * Hd:], L=L, H=heads, D=dh, nseq=B,
                                scale=1.0 / math.sqrt(dh), seq=(1, L, 0, 1), kmask=kmask, dropout=(pa, s_attn))
-        if ph > 0 and _BERT_FUSE:   # LN(dropout(dense(ctx)) + x): the dropout in the split-K combine
+        if ph > 0:   # LN(dropout(dense(ctx)) + x): the dropout in the split-K combine
             a = K.linear(ctxv, Wo_b, bias=bo, residual=xf, out_dtype=F32, w_lo=Wo_lo, dropout=(ph, s_out1))
-        elif ph > 0:     # (A/B: the stand-alone dropout kernel; the residual leaves the GEMM epilogue)
-            a = K.dropout(K.linear(ctxv, Wo_b, bias=bo, out_dtype=F32, w_lo=Wo_lo), ph, s_out1, res=xf)[0]
         else:
             a = K.linear(ctxv, Wo_b, bias=bo, residual=xf, out_dtype=F32, w_lo=Wo_lo)
         x1b, x1f, m1, r1 = K.layernorm_fwd(a, ln1_w, ln1_b, eps, out_bf16=True, out_f32=True)
         hpre = torch.empty(xf.shape[0], Wi.shape[0], device=xf.device, dtype=BF16)
         hact = K.linear(x1b, Wi_b, bias=bi, act=K.ACT_GELU, out2=hpre, w_lo=Wi_lo)
-        if ph > 0 and _BERT_FUSE:
+        if ph > 0:
             b2 = K.linear(hact, Wout_b, bias=bout, residual=x1f, out_dtype=F32, w_lo=Wout_lo, dropout=(ph, s_out2))
-        elif ph > 0:
-            b2 = K.dropout(K.linear(hact, Wout_b, bias=bout, out_dtype=F32, w_lo=Wout_lo), ph, s_out2, res=x1f)[0]
         else:
             b2 = K.linear(hact, Wout_b, bias=bout, residual=x1f, out_dtype=F32, w_lo=Wout_lo)
         x2b, x2f, m2, r2 = K.layernorm_fwd(b2, ln2_w, ln2_b, eps, out_bf16=True, out_f32=True)
@@ -1478,7 +1431,7 @@ class BertLayerFn(torch.autograd.Function):
             if b.requires_grad and not bias_done:
                 K.colsum(dy, out=gsink(b), accumulate=True)
 
-        fuse = ph > 0 and _BERT_FUSE
+        fuse = ph > 0
         # LN2 + FF out; with dropout the LN backward also emits the dense branch's masked bf16
         # gradient and its column sums (the dense bias gradient)
         if fuse:
@@ -1488,12 +1441,7 @@ class BertLayerFn(torch.autograd.Function):
         else:
             db2f, db2b, _, _ = K.layernorm_bwd(dx2f.contiguous(), b2, m2, r2, ln2_w, dgamma_out=gsink(ln2_w),
                                                dbeta_out=gsink(ln2_b))
-            if ph > 0:       # gradient through the output dropout (the residual path bypasses it)
-                db2b = K.dropout(db2f, ph, s_out2, out_f32=False, out_bf16=True)[1]
-        if _BERT_FUSE:       # dhpre = (db2 . Wout) * gelu'(hpre) in one GEMM (act 6)
-            dhpre = K.matmul_nn_gelu_bwd(db2b, Wout_b, hpre)
-        else:
-            dhpre = K.gelu_bwd(K.matmul_nn(db2b, Wout_b), hpre)
+        dhpre = K.matmul_nn_gelu_bwd(db2b, Wout_b, hpre)   # (db2 . Wout) * gelu'(hpre) in one GEMM (act 6)
         wgrad(db2b, hact, Wout, bout, bias_done=fuse)
         dx1 = K.matmul_nn(dhpre, Wi_b, residual=db2f, out_dtype=F32)
         wgrad(dhpre, x1b, Wi, bi)
@@ -1504,8 +1452,6 @@ class BertLayerFn(torch.autograd.Function):
         else:
             daf, dab, _, _ = K.layernorm_bwd(dx1, a, m1, r1, ln1_w, dgamma_out=gsink(ln1_w),
                                              dbeta_out=gsink(ln1_b))
-            if ph > 0:
-                dab = K.dropout(daf, ph, s_out1, out_f32=False, out_bf16=True)[1]
         dctx = K.matmul_nn(dab, Wo_b)
         wgrad(dab, ctxv, Wo, bo, bias_done=fuse)
         dqkv = torch.empty_like(qkv)
@@ -1513,7 +1459,7 @@ class BertLayerFn(torch.autograd.Function):
                    dqkv[:, Hd:2 * Hd], dqkv[:, 2 * Hd:], L=L, H=heads, D=dh, nseq=B, scale=1.0 / math.sqrt(dh),
                    seq=(1, L, 0, 1), kmask=kmask, dropout=(pa, s_attn))
         dx = K.matmul_nn(dqkv, Wqkv, residual=daf, out_dtype=F32)
-        gW, gB = (gsink_cat([Wq, Wk, Wv]), gsink_cat([bq, bk, bv])) if _QKV_WGRAD else (None, None)
+        gW, gB = gsink_cat([Wq, Wk, Wv]), gsink_cat([bq, bk, bv])
         if gW is not None and gB is not None:
             # q / k / v gradients adjacent in the arena: one [3 Hd, Hd] weight-gradient GEMM (108
             # tiles instead of 3 x 36) and one column sum, same per-element arithmetic

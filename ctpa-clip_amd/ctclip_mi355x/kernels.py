@@ -439,8 +439,7 @@ def reduce_slabs(slabs, out, accumulate=False):
 # tower's stream).  Inside a backward pass they are queued per stream instead and summed by ONE
 # batched launch (ctclip_reduce_slabs_multi, bit-identical to the single reduction) when the pass
 # ends (autograd callback), or earlier when a gradient bucket's all-reduce is about to read them
-# (dist_sync.BucketedGradSync).  CTCLIP_DEFER_REDUCE=0 restores the immediate launches.
-DEFER_REDUCE = os.environ.get('CTCLIP_DEFER_REDUCE', '1') != '0'
+# (dist_sync.BucketedGradSync).
 _DEFERRED = {}        # stream id -> (stream, [(slabs, out, accumulate), ...])
 _CB_QUEUED = [None]   # graph task id whose end-of-pass callback is queued (None: none)
 
@@ -508,7 +507,7 @@ def _end_of_backward():
 def reduce_param_partials(part, out, accumulate):
     """out[D] (+)= sum of part[nb][D]: deferred inside a backward pass (see above)."""
     nb, D = part.shape[0], part.shape[-1]
-    if (DEFER_REDUCE and nb >= 16 and out.dtype == F32 and out.is_contiguous() and part.is_contiguous()
+    if (nb >= 16 and out.dtype == F32 and out.is_contiguous() and part.is_contiguous()
             and D % 4 == 0 and _in_backward()):
         st = torch.cuda.current_stream(part.device)
         _DEFERRED.setdefault(st.cuda_stream, (st, []))[1].append((part, out.view(-1), accumulate))
@@ -526,13 +525,7 @@ def nblocks_for(rows, cap=1024):
     >= 64 rows per workgroup on long inputs (the 3D-ViT's 110,592 tokens: the parameter-gradient
     partial slabs stay small), but one row per wave on short ones (BERT's 1,024 tokens: 256
     workgroups instead of 16, whose waves walked 16 rows one memory latency after another)."""
-    if not _LNB_WIDE:
-        return int(max(1, min(cap, (rows + 63) // 64)))
     return int(max(1, min(cap, max((rows + 63) // 64, min(256, (rows + 3) // 4)))))
-
-
-_LNB_WIDE = os.environ.get('CTCLIP_LNB_WIDE', '1') != '0'   # A/B switch of nblocks_for's short-input rule
-_LNB_CAP = int(os.environ.get('CTCLIP_LNB_CAP', '1024'))      # LayerNorm-backward workgroup cap (A/B)
 
 
 def colsum(x, out=None, accumulate=False):
@@ -577,7 +570,7 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, *, dres=None, want_beta=True, dx_f32
     """Returns (dx_f32, dx_bf16, dgamma, dbeta).  dgamma_out / dbeta_out: accumulate the
     parameter gradients into these f32 tensors instead of returning fresh ones."""
     rows, D = x.shape
-    nb = nblocks_for(rows, _LNB_CAP)
+    nb = nblocks_for(rows)
     dxf = torch.empty(rows, D, device=x.device, dtype=F32) if dx_f32 else None
     dxb = torch.empty(rows, D, device=x.device, dtype=BF16) if dx_bf16 else None
     pg = torch.empty(nb, D, device=x.device, dtype=F32)
@@ -607,7 +600,7 @@ def layernorm_bwd_drop(dy, x, mean, rstd, gamma, p, seed, *, dgamma_out, dbeta_o
     into dgamma_out / dbeta_out / dbias_out (deferred partial reductions)."""
     rows, D = x.shape
     assert dy.dtype == F32 and x.dtype == F32
-    nb = nblocks_for(rows, _LNB_CAP)
+    nb = nblocks_for(rows)
     dxf = torch.empty(rows, D, device=x.device, dtype=F32)
     dxb = torch.empty(rows, D, device=x.device, dtype=BF16)
     pg = torch.empty(nb, D, device=x.device, dtype=F32)
@@ -1096,19 +1089,14 @@ def attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, *, L, H, D, nseq, scale, seq, bi
                    kmask=kmask, lse=lse, dout=dout, dq=dq, dk=dk, dv=dv, delta=delta, dbias_u=dbias_u,
                    dropout=dropout)
     ws = None
-    if dbias_u is not None and _ATTN_BIAS_WS:
-        # per-workgroup partial bins + one deterministic reduction instead of global float atomics
+    if dbias_u is not None:
+        # per-workgroup partial bins + one deterministic reduction instead of global float atomics: within
+        # noise of them (spatial backward 822 vs 810 us, profiles/r02bc_attn_ws_ab.log) and bit-reproducible
         n = _lib.lib().ctclip_attn_bwd_ws_floats(_lib.ctypes.byref(a))
         if n > 0:
             ws = torch.empty(n, device=q.device, dtype=F32)
             a.dbias_ws, a.dbias_ws_floats = ptr(ws), n
     call('ctclip_attn_bwd', _lib.ctypes.byref(a), stream_ptr())
-
-
-# the bias-gradient workspace (deterministic slab reduction) costs within noise of the global
-# float atomics (spatial backward 822 vs 810 us, profiles/r02bc_attn_ws_ab.log) and makes the bias
-# gradient bit-reproducible: default since round 3 (CTCLIP_ATTN_BIAS_WS=0 = the atomics)
-_ATTN_BIAS_WS = os.environ.get('CTCLIP_ATTN_BIAS_WS', '1') != '0'
 
 
 # ----------------------------------------------------------------------------- VQ

@@ -20,8 +20,7 @@ from . import dist_sync
 from . import streams
 from . import kernels as K
 
-# diagnostic A/B only (CTCLIP_DIAG_TEXT_ADAM=skip | main): NOT the reference's work when 'skip'
-_DIAG_TEXT_ADAM = os.environ.get('CTCLIP_DIAG_TEXT_ADAM', '')
+
 def _ema_site():
     from . import ct_clip
     return ct_clip.DEFER_EMA
@@ -337,12 +336,6 @@ class CTClipTrainer:
             if off > lo:
                 self._adam(lo, off - lo)
             lo = off + n
-        if skip and _DIAG_TEXT_ADAM == 'skip':     # diagnostic only: what the overlap costs
-            return
-        if skip and _DIAG_TEXT_ADAM == 'main':     # diagnostic only: serialised on the main stream
-            off, n = skip[0]
-            self._adam(off, n)
-            return
         if skip and self.defer_text_adam:
             # queued by the next step's BERT forward, after the next image tower's patch embedding
             # (streams.defer_text); ``flush`` queues it when no step follows

@@ -1,5 +1,5 @@
 """Same-box A/B of the bench step under environment settings (each setting its own child
-process, interleaved rounds):  python tools/env_ab.py "" "CTCLIP_EPI_LDS=3" ...   (GPU)"""
+process, interleaved rounds):  python tools/env_ab.py "" "CTCLIP_LN1_FOLD=0" ...   (GPU)"""
 import json
 import os
 import subprocess

@@ -1,6 +1,6 @@
 """Main-loop efficiency probe for the large-tile GEMM variants: 4096 x 4096 (256 tiles of 256^2,
-one per CU) NT GEMM over K = 512..8192, bf16 out.  Run twice, with and without
-CTCLIP_G256_DEBUG=1 (skip epilogue), to split the per-K-step cost from the fixed cost."""
+one per CU) NT GEMM over K = 512..8192, bf16 out: the slope over K is the per-K-step
+cost, the intercept the fixed cost."""
 import os
 import sys
 

@@ -1,7 +1,7 @@
 """Main-loop rate of the 8-phase GEMM per operand layout: 4096 x 4096 output (256 tiles, one
 per CU), K = 8192 / 16384, f32 output.  NT = both operands K-contiguous (forward), NN = dX
 (B MN-contiguous), TN = dW (both MN-contiguous, the split-K weight-gradient layout).
-Run with CTCLIP_G256_DEBUG=1 as well to drop the epilogue.   usage: python tools/gemm_probe_layouts.py (GPU)"""
+usage: python tools/gemm_probe_layouts.py (GPU)"""
 import os
 import sys
 
