@@ -194,33 +194,6 @@ __device__ __forceinline__ bf16x8 trfrag_sw(const char* img, int r0, int c0, int
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// stage2 into swizzled 64-B-row images (head dim 32)
-template <int U>
-__device__ __forceinline__ void stage2_sw(char* imgA, const u16* a, int64_t lda, char* imgB, const u16* b, int64_t ldb,
-                                          const AP& p, int s, int h, int Lp, int tid, int nth) {
-  constexpr int D = 32, CH = 4;
-  const int n1 = Lp * CH, n = 2 * n1;
-  for (int i0 = tid; i0 < n; i0 += U * nth) {
-    u32x4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int idx = i0 + u * nth, isb = idx >= n1, id = isb ? idx - n1 : idx;
-      const int r = id / CH, c = id - r * CH;
-      v[u] = make_uint4(0, 0, 0, 0);
-      if (idx < n && r < p.L) {
-        const int64_t row = seq_row(p, s, r);
-        v[u] = isb ? *(const u32x4*)(b + row * ldb + h * D + c * 8) : *(const u32x4*)(a + row * lda + h * D + c * 8);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int idx = i0 + u * nth, isb = idx >= n1, id = isb ? idx - n1 : idx;
-      const int r = id / CH, c = id - r * CH;
-      if (idx < n) *(u32x4*)((isb ? imgB : imgA) + r * 64 + ((c ^ kv_swz(r)) << 4)) = v[u];
-    }
-  }
-}
-
 __device__ __forceinline__ bf16x8 pack_perm(const f32x4& a, const f32x4& b) {
   bf16x8 r;
   r[0] = (bf16)a[0]; r[1] = (bf16)a[1]; r[2] = (bf16)a[2]; r[3] = (bf16)a[3];
@@ -272,6 +245,14 @@ __device__ __forceinline__ void load_tables(const AP& p, char* tab, int Lp, int 
     }
   }
 }
+// LDS bytes of those tables: [BIAS: ub + kb] + madd[pp][Lp] (+ bins[nbins] after them, dQ kernel)
+size_t table_bytes(const AP& p, int Lp, bool bins) {
+  size_t b = (size_t)p.pp * Lp * 4;
+  const size_t nb4 = (size_t)((p.nbins + 3) & ~3);
+  if (p.bias_u) b += nb4 * 4 + (size_t)Lp * 4 + (bins ? nb4 * 4 : 0);
+  return b;
+}
+inline int pad32(int L) { return (L + 31) & ~31; }
 
 // ------------------------------------------------------------------------------------ forward
 // W waves per workgroup: 12 for the spatial (BIAS) shapes, whose 36 query blocks then split
@@ -291,12 +272,8 @@ __device__ __forceinline__ void load_tables(const AP& p, char* tab, int Lp, int 
 // span (2 scale ||q|| max||k|| + bias range) stays <= 64, so no probability can underflow more
 // than exp2(-64) below the row's largest; otherwise that group runs the online-max code.  Same
 // softmax in exact arithmetic, f32-level differences in rounding.
-// A/B build switch: 1 = the swizzled 64-B-row K / V images for head dim 32.
-// Measured 1.2 % SLOWER in this VALU-bound kernel (profiles/r04h_attn_lazy_ab.log: 252.4 vs 249.5 us),
-// so the padded 80-B rows stay the default
-#ifndef CTCLIP_ATTN_FWD_SWZ
-#define CTCLIP_ATTN_FWD_SWZ 0
-#endif
+// K / V images: the padded 80-B rows.  Tried for head dim 32: the backward's swizzled 64-B rows
+// (kv_swz), 1.2 % SLOWER in this VALU-bound kernel (profiles/r04h_attn_lazy_ab.log: 252.4 vs 249.5 us).
 // CINIT (RUN shapes, round 6): the score chain with the least vector work per score -- the bias
 // enters as the MFMA's C operand (read from the reversed, 1/scale table straight into the
 // accumulator), so score -> probability is one v_fma (scale log2 e, minus the running max) and one
@@ -309,9 +286,7 @@ template <int D, bool BIAS, int W = (BIAS ? 12 : NW), bool RUN = false, int QB =
 __global__ __launch_bounds__(W * 64) void attn_fwd_kernel(AP p) {
   static_assert(!CINIT || (RUN && !SMAX && BIAS), "CINIT: the RUN shapes' online-max forward");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // head dim 32: swizzled 64-B-row K / V images (kv_swz); 64: the padded rows
-  constexpr bool SWZ = D == 32 && CTCLIP_ATTN_FWD_SWZ;
-  constexpr int KK = D / 32, DB = D / 16, RS = SWZ ? 64 : Img<D>::RS, NTH = W * 64;
+  constexpr int KK = D / 32, DB = D / 16, RS = Img<D>::RS, NTH = W * 64;
   const int L = p.L, Lp = (L + 31) & ~31;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wpp = W / p.pp;                          // waves per pair
@@ -321,21 +296,11 @@ __global__ __launch_bounds__(W * 64) void attn_fwd_kernel(AP p) {
     const int pair = blockIdx.x * p.pp + pl;
     if (pair >= p.nseq * p.H) break;
     const int s = pair / p.H, h = pair - s * p.H;
-    if constexpr (SWZ)
-      stage2_sw<SU>(smem + pl * pair_bytes, p.k, p.ldk, smem + pl * pair_bytes + Lp * RS, p.v, p.ldv, p, s, h, Lp,
-                    tid, NTH);
-    else
-      stage2<D, SU>(smem + pl * pair_bytes, p.k, p.ldk, smem + pl * pair_bytes + Lp * RS, p.v, p.ldv, p, s, h, Lp,
-                    tid, NTH);
+    stage2<D, SU>(smem + pl * pair_bytes, p.k, p.ldk, smem + pl * pair_bytes + Lp * RS, p.v, p.ldv, p, s, h, Lp,
+                  tid, NTH);
   }
-  auto kfrag = [&](const char* img, int r0, int kk) {
-    if constexpr (SWZ) return rowfrag_sw(img, r0, lane);
-    else return rowfrag<D>(img, r0, kk, lane);
-  };
-  auto vfrag = [&](const char* img, int r0, int c0) {
-    if constexpr (SWZ) return trfrag_sw(img, r0, c0, lane);
-    else return trfrag<D>(img, r0, c0, lane);
-  };
+  auto kfrag = [&](const char* img, int r0, int kk) { return rowfrag<D>(img, r0, kk, lane); };
+  auto vfrag = [&](const char* img, int r0, int c0) { return trfrag<D>(img, r0, c0, lane); };
   float* ub = nullptr;
   int* kb = nullptr;
   float* madd = nullptr;
@@ -687,6 +652,12 @@ __global__ __launch_bounds__(W * 64) void attn_fwd_kernel(AP p) {
     }
   }
 }
+// its LDS: pp x (K + V images), the tables, the SMAX block reduction's 3 W floats (256 B)
+template <int D>
+size_t fwd_lds(const AP& p) {
+  const int Lp = pad32(p.L);
+  return (size_t)p.pp * 2 * Lp * Img<D>::RS + table_bytes(p, Lp, false) + 256;
+}
 
 // ------------------------------------------------------------------------------- backward dQ
 // also writes delta = rowsum(dO * O); with BIAS, bins the bias gradient (LDS atomics; the
@@ -805,6 +776,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AP p) {
       if (v != 0.f) atomicAdd(&p.dbias_u[(int64_t)hh * p.nbins + i], v);
     }
   }
+}
+// its LDS: pp x (K + V images), the tables, the bins
+template <int D>
+size_t dq_lds(const AP& p) {
+  const int Lp = pad32(p.L);
+  return (size_t)p.pp * 2 * Lp * Img<D>::RS + table_bytes(p, Lp, true);
 }
 
 // ----------------------------------------------------------------------------- backward dK dV
@@ -925,6 +902,12 @@ __global__ __launch_bounds__(W * 64) void attn_bwd_dkv_kernel(AP p) {
       }
     }
   }
+}
+// its LDS: pp x (Q + dO images, lse, delta), the tables
+template <int D>
+size_t dkv_lds(const AP& p) {
+  const int Lp = pad32(p.L);
+  return (size_t)p.pp * (2 * Lp * Img<D>::RS + 2 * Lp * 4) + table_bytes(p, Lp, false);
 }
 
 // ------------------------------------------------------------ backward dQ, biased (spatial) case
@@ -1098,6 +1081,11 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_bias_kernel(AP p, int nfc) {
     else if (v != 0.f) atomicAdd(&p.dbias_u[(int64_t)h * p.nbins + i], v);
   }
 }
+// its LDS: K + V images, ub + bins, kb + madd, the dQ exchange
+size_t dq_bias_lds(const AP& p) {
+  const int Lp = pad32(p.L);
+  return (size_t)2 * Lp * Img<32>::RS + 2 * (size_t)((p.nbins + 3) & ~3) * 4 + 2 * (size_t)Lp * 4 + 4 * 64 * 8 * 4;
+}
 
 // ------------------------------------------ backward dQ, biased, base spatial shape (L = LF = 576)
 // attn_bwd_dq_bias_kernel specialised to a full 24 x 24 grid (r02), same grid, LDS tables,
@@ -1116,40 +1104,21 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_bias_kernel(AP p, int nfc) {
 // 140 B of scratch per lane whose per-frame reloads wait behind the LDS-DMA queue -- 887 vs 697 us
 // per spatial backward (profiles/r05e_attn_kp_ab.log), so 8 waves stay
 constexpr int DQD_W = 8, DQD_NT = DQD_W * 64, DQD_KP = 2;
-// the spatial backward kernels fold each query's lse and delta into the score / dP MFMAs'
-// accumulator inputs (one VALU subtraction per score and per dP less; round 5), 0 = subtract them
-// per element (A/B build switch)
-#ifndef CTCLIP_ATTN_CFOLD
-#define CTCLIP_ATTN_CFOLD 1
-#endif
-// the same in the dQ kernel: its two constant accumulator inputs hold 8 more VGPRs across the frame
-// loop at a 256-VGPR budget (scratch 40 -> 128 B per lane), so off
-#ifndef CTCLIP_ATTN_CFOLD_DQ
-#define CTCLIP_ATTN_CFOLD_DQ 0
-#endif
-// key positions of the bias reads: 1 = kb_fast (VALU), 0 = the LDS table (A/B build switch).
-// Measured (profiles/r05d_attn_ab.log): the table, 699-705 us per spatial backward vs 718 for
-// kb_fast, whose per-chunk VALU spills 40 -> 56 B per lane at this kernel's 256-VGPR budget
-#ifndef CTCLIP_ATTN_DQ_KBFAST
-#define CTCLIP_ATTN_DQ_KBFAST 0
-#endif
-// bias-gradient binning of the dQ kernel: 1 = diagonal sums over an LDS image of the block's
-// frame-summed dS (no LDS float atomics); 0 = LDS atomics per (query, key) (A/B build switch).
-// Measured (profiles/r02ba_attn_bin_ab.log): spatial backward 837 -> 807 us per layer; without
-// any binning it would be 692 us -- the remainder is the 1,008 workgroups x 2,209 global atomics
-#ifndef CTCLIP_ATTN_DIAG_BIN
-#define CTCLIP_ATTN_DIAG_BIN 1
-#endif
-// round 6: the score MFMA's accumulator input is the CPB bias itself (the forward's C-init chain:
-// reversed 1/scale table, one fma with the query's -lse per score instead of fma + sub)
-#ifndef CTCLIP_ATTN_DQ_CINIT
-#define CTCLIP_ATTN_DQ_CINIT 1
-#endif
+// LDS layout, shared by the kernel and its launcher: two frame buffers of a K and a V image
+// (64-B rows), then the bias table and the key positions
+template <int LF>
+struct DqDmaLds {
+  static constexpr int IMG = LF * 64, BUF = 2 * IMG;
+  static constexpr size_t bytes(int nbins) { return (size_t)2 * BUF + (size_t)((nbins + 3) & ~3) * 4 + LF * 4; }
+};
+// true of every L = 576 bias shape (nbins <= 2,209, see the dK/dV kernel below): it fits the
+// 160 KiB of LDS, and the bins fit one frame buffer
+static_assert(DqDmaLds<576>::bytes(2209) <= 160 * 1024 && 2209 * 4 <= DqDmaLds<576>::BUF, "LDS budget");
 template <int LF, int KP = DQD_KP>
 __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p, int nfc) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int D = 32, DB = 2, L = LF, NC = L / 32, NCP = NC / KP, NW = 4 * KP, NTH = NW * 64;
-  constexpr int IMG = L * 64, BUF = 2 * IMG, NG = BUF / 1024 / NW;   // glds per wave per frame
+  constexpr int IMG = DqDmaLds<LF>::IMG, BUF = DqDmaLds<LF>::BUF, NG = BUF / 1024 / NW;   // glds per wave per frame
   static_assert(L % 64 == 0 && NC % KP == 0 && (BUF / 1024) % NW == 0 && (IMG / 1024) % NG == 0 &&
                 (KP - 1) * 4 * 64 * 8 * 4 <= BUF, "full-shape specialisation");
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1159,14 +1128,10 @@ __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p,
   float* ub = (float*)(smem + 2 * BUF);
   const int nb4 = (p.nbins + 3) & ~3;
   int* kb = (int*)(ub + nb4);
-#if CTCLIP_ATTN_DQ_CINIT
   {
     const float isc = 1.f / p.scale;   // the forward's table (load_tables REV), bit for bit
     for (int i = tid; i < p.nbins; i += NTH) ub[i] = p.bias_u[(int64_t)h * p.nbins + p.nbins - 1 - i] * isc;
   }
-#else
-  for (int i = tid; i < p.nbins; i += NTH) ub[i] = p.bias_u[(int64_t)h * p.nbins + i] * LOG2E;
-#endif
   for (int i = tid; i < L; i += NTH) kb[i] = kb_of(p, i);
   const int g = lane >> 4, li = lane & 15;
   const int q = qg * 64 + qsub * 16 + li;   // < L: L % 64 == 0
@@ -1205,9 +1170,7 @@ __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p,
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();   // tables (frame f0's DMA may still be in flight)
   __builtin_amdgcn_sched_barrier(0);
-  const int cq = kb[q] + boff(p);
-  [[maybe_unused]] const int cqr = p.nbins - 1 - cq;   // (C-init: reversed-table index of key 0)
-  [[maybe_unused]] const KbFast kbf = kb_fast_init(p);
+  const int cqr = p.nbins - 1 - (kb[q] + boff(p));   // reversed-table index of key 0's bin
   for (int s = f0; s < f1; ++s) {
     const int b = (s - f0) & 1;
     const char* Kimg = smem + b * BUF;
@@ -1235,14 +1198,6 @@ __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p,
     }
     const int64_t qrow = (int64_t)s * p.s_outer + q;
     if (g == 0 && kpart == 0) p.delta[(int64_t)h * p.M + qrow] = dl;
-#if CTCLIP_ATTN_CFOLD_DQ
-    // the query's lse and delta ride in the score / dP MFMAs' accumulator inputs (S^T layout: all 4
-    // registers of a lane are its query): x - l2 = sc2 (q.k - lse / scale) + bias, dP - delta
-    const float cl = -lse2 / p.scale;
-    const f32x4 cS = f32x4{cl, cl, cl, cl}, cD = f32x4{-dl, -dl, -dl, -dl};
-#else
-    const f32x4 cS = f32x4{0.f, 0.f, 0.f, 0.f}, cD = cS;
-#endif
     __builtin_amdgcn_sched_barrier(0);
     if (s + 1 < f1) {
       load_q(s + 1);
@@ -1256,59 +1211,31 @@ __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p,
     for (int ci = 0; ci < NCP; ++ci) {
       const int kc = (c_begin + ci) * 32;
       f32x4 sa[2], da[2];
-#if CTCLIP_ATTN_DQ_CINIT
-      (void)cS;
+      // The score MFMA's accumulator input is the CPB bias itself (the forward's C-init chain):
+      // one fma with the query's -lse per score instead of fma + sub.  Tried against it:
+      //  * the forward-order log2 e table added per score, its key positions from the LDS table
+      //    (699-705 us per spatial backward) or from kb_fast (718 us: the per-chunk VALU spills
+      //    40 -> 56 B per lane at this kernel's 256-VGPR budget; profiles/r05d_attn_ab.log);
+      //  * -lse / scale and -delta folded into the two MFMAs' accumulator inputs, as the dK/dV
+      //    kernel does: the two constants hold 8 more VGPRs across the frame loop (scratch
+      //    40 -> 128 B per lane), so delta is subtracted per element.
       const float nl2 = -l2;
 #pragma unroll
       for (int bi = 0; bi < 2; ++bi) {
         const float* up = ub + (kb[kc + 16 * bi + 4 * g] + cqr);   // up[r] = bias(q, k0 + r) / scale
         sa[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Kimg, kc + 16 * bi, lane), qc,
                                                          f32x4{up[0], up[1], up[2], up[3]}, 0, 0, 0);
-        da[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Vimg, kc + 16 * bi, lane), dc, cD, 0, 0, 0);
+        da[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Vimg, kc + 16 * bi, lane), dc,
+                                                         f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       }
 #pragma unroll
       for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-#if CTCLIP_ATTN_CFOLD_DQ
-          const float ds = fexp2(fmaf(sa[bi][r], sc2, nl2)) * da[bi][r];
-#else
           const float ds = fexp2(fmaf(sa[bi][r], sc2, nl2)) * (da[bi][r] - dl);
-#endif
-          acc[ci][bi][r] += ds;
-          sa[bi][r] = ds;
-        }
-#else
-#pragma unroll
-      for (int bi = 0; bi < 2; ++bi) {
-        sa[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Kimg, kc + 16 * bi, lane), qc, cS, 0, 0, 0);
-        da[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Vimg, kc + 16 * bi, lane), dc, cD, 0, 0, 0);
-      }
-#pragma unroll
-      for (int bi = 0; bi < 2; ++bi) {
-        int k0 = kc + 16 * bi + 4 * g;
-#if CTCLIP_ATTN_DQ_KBFAST
-        asm volatile("" : "+v"(k0));   // computed here, per chunk: hoisted out of the frame loop the
-                                       // 18 positions spill
-        // up[3 - r] = ub[bin(q, k0 + r)] (RUN); the key's position by VALU, not a table read the
-        // bias read's address would wait on (a two-deep LDS chain per chunk)
-        const float* up = ub + (cq - kb_fast(kbf, k0) - 3);
-#else
-        const float* up = ub + (cq - kb[k0] - 3);   // up[3 - r] = ub[bin(q, k0 + r)] (RUN)
-#endif
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float x = sa[bi][r] * sc2 + up[3 - r];
-#if CTCLIP_ATTN_CFOLD_DQ
-          const float ds = fexp2(x) * da[bi][r];
-#else
-          const float ds = fexp2(x - l2) * (da[bi][r] - dl);
-#endif
           acc[ci][bi][r] += ds;
           sa[bi][r] = ds;   // the score scale is applied once per dQ output below (exact for 8)
         }
-      }
-#endif
       const bf16x8 dsb = pack_perm(sa[0], sa[1]);
 #pragma unroll
       for (int d = 0; d < DB; ++d)
@@ -1349,10 +1276,12 @@ __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p,
   // bin the frame-summed dS once (bins in buffer 0: every wave is past its last read of it)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
-#if CTCLIP_ATTN_DIAG_BIN
   // without LDS float atomics: the block's 64 x L frame-summed dS go to LDS (both K / V buffers,
   // free now: 64 x 576 x 4 B = 147,456 B = 2 BUF), then each thread sums whole bins along their
-  // diagonals, bin (dh, dw) = sum over the 64 queries q of dS[q][q - (dh, dw)], in a fixed order
+  // diagonals, bin (dh, dw) = sum over the 64 queries q of dS[q][q - (dh, dw)], in a fixed order.
+  // Tried against it: LDS atomics per (query, key), spatial backward 837 vs 807 us per layer
+  // (profiles/r02ba_attn_bin_ab.log); without any binning it would be 692 us -- the remainder is
+  // the 1,008 workgroups x 2,209 global atomics, which the dbias_ws slabs replace
   {
     // rows padded to LP = L + 3 floats: the 16 query rows of a half-wave's stores land in distinct
     // banks (an L-float stride put all 16 in one); the image may run over the bias / position
@@ -1388,183 +1317,44 @@ __global__ __launch_bounds__(4 * KP * 64) void attn_bwd_dq_bias_dma_kernel(AP p,
       else if (sum != 0.f) atomicAdd(&p.dbias_u[(int64_t)h * p.nbins + b], sum);
     }
   }
-#else
-  float* bins = (float*)smem;
-  for (int i = tid; i < p.nbins; i += NTH) bins[i] = 0.f;
-  __syncthreads();
-#ifndef CTCLIP_ATTN_NO_BIN   // diagnostic build only: skip the binning (wrong bias gradient) to time it
-#pragma unroll
-  for (int ci = 0; ci < NCP; ++ci)
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = (c_begin + ci) * 32 + 16 * bi + 4 * g + r;
-        atomicAdd(&bins[cq - kb[key]], acc[ci][bi][r]);
-      }
-#else
-  if (acc[0][0][0] == 12345.f) bins[0] = 1.f;   // keep acc live
-#endif
-  __syncthreads();
-  for (int i = tid; i < p.nbins; i += NTH) {
-    const float v = bins[i];
-    if (v != 0.f) atomicAdd(&p.dbias_u[(int64_t)h * p.nbins + i], v);
-  }
-#endif
 }
-
-// --------------------------------------------- backward dK dV, biased, base spatial shape (L = LF)
-// attn_bwd_dkv_kernel<32, true, 12, true> made persistent over frames (r02): 32 workgroups per
-// head walk frames s = blockIdx.x / H, + gridDim.x / H, ... with their head's bias table loaded
-// once, and the NEXT frame's Q / dO rows (6 x 16 B per thread) and lse / delta are loaded into
-// registers while this frame computes, then written to the LDS images behind one barrier (the
-// per-pair kernel pays every (frame, head) pair's staging latency with nothing to overlap it:
-// 1 workgroup per CU).  Each wave's K / V fragments of its next key block are loaded one block
-// ahead.  The Q / dO images are unpadded 64-B rows with the dQ kernel's chunk swizzle (the
-// padded 80-B rows conflict under gfx950's ds_read_b128 lane groups: 35 % of the per-pair
-// kernel's LDS cycles, r02 PMC).  Same arithmetic and results as the per-pair kernel.
-constexpr int DKP_W = 12, DKP_NT = DKP_W * 64;
-template <int LF>
-__global__ __launch_bounds__(DKP_NT) void attn_bwd_dkv_persist_kernel(AP p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int D = 32, DB = 2, RS = 64, W = DKP_W, NTH = DKP_NT, L = LF, CH = D / 8;
-  constexpr int NLD = 2 * L * CH / NTH, RPU = NTH / CH, NKB = L / 16;
-  static_assert((2 * L * CH) % NTH == 0 && L % 32 == 0 && L % 16 == 0 && (W * 64 / CH) % 16 == 0, "shape");
-  const int tid = threadIdx.x, lane = tid & 63, wi = tid >> 6;
-  const int h = blockIdx.x % p.H, wg = blockIdx.x / p.H, nwg = gridDim.x / p.H;
-  char* Qimg = smem;
-  char* Dimg = smem + L * RS;
-  float* ls = (float*)(smem + 2 * L * RS);
-  float* dls = ls + L;
-  float* ub = dls + L;
-  const int nb4 = (p.nbins + 3) & ~3;
-  int* kb = (int*)(ub + nb4);
-  for (int i = tid; i < p.nbins; i += NTH) ub[i] = p.bias_u[(int64_t)h * p.nbins + i] * LOG2E;
-  for (int i = tid; i < L; i += NTH) kb[i] = kb_of(p, i);
-  const int g = lane >> 4, li = lane & 15;
-  const float sc2 = p.scale * LOG2E;
-  const KbFast kbf = kb_fast_init(p);
-  // staging map: chunk u of a thread is row R = tid / CH + RPU u of the stacked [Q; dO] image
-  // (dO when R >= L: wave-uniform as 64 / CH rows per wave divide L), 16-B column tid % CH
-  const int r0 = tid / CH, c0 = tid % CH;
-  const int64_t offq = (int64_t)r0 * p.ldq + h * D + c0 * 8, offd = (int64_t)r0 * p.lddo + h * D + c0 * 8;
-  u32x4 st[NLD];
-  float lsv = 0.f, dlv = 0.f;   // this thread's lse / delta row (tid < L)
-#define CT_DKV_LOAD(S_)                                                                          \
-  do {                                                                                           \
-    const int64_t fb_ = (int64_t)(S_) * p.s_outer;   /* row(s, i) = s * s_outer + i (host-checked) */ \
-    _Pragma("unroll") for (int u = 0; u < NLD; ++u) {                                            \
-      const bool isq = u * RPU + (wi * 64) / CH < L;                                             \
-      const u16* src_ = isq ? p.q + (fb_ + u * RPU) * p.ldq + offq : p.dout + (fb_ + u * RPU - L) * p.lddo + offd; \
-      st[u] = *(const u32x4*)src_;                                                               \
-    }                                                                                            \
-    if (tid < L) {                                                                               \
-      lsv = p.lse[(int64_t)h * p.M + fb_ + tid];                                                 \
-      dlv = p.delta[(int64_t)h * p.M + fb_ + tid];                                               \
-    }                                                                                            \
-  } while (0)
-  int s = wg;
-  if (s < p.nseq) CT_DKV_LOAD(s);
-  for (; s < p.nseq; s += nwg) {
-    __syncthreads();   // previous frame's LDS reads done (and, first time, the tables written)
-#pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const bool isq = u * RPU + (wi * 64) / CH < L;
-      char* dst = isq ? Qimg + (u * RPU) * RS : Dimg + (u * RPU - L) * RS;
-      *(u32x4*)(dst + r0 * RS + ((c0 ^ kv_swz(u * RPU + r0)) << 4)) = st[u];   // R = u RPU + r0, same swizzle for the dO part (L % 8 == 0)
-    }
-    if (tid < L) {
-      ls[tid] = lsv * LOG2E;
-      dls[tid] = dlv;
-    }
-    __syncthreads();
-    if (s + nwg < p.nseq) CT_DKV_LOAD(s + nwg);   // in flight under this frame's key blocks
-    const int64_t fb = (int64_t)s * p.s_outer;
-    // K / V fragments one key block ahead
-    bf16x8 kf = zero8(), vf = zero8();
-    {
-      const int64_t krow = fb + wi * 16 + li;
-      kf = gload8(p.k + krow * p.ldk + h * D + 8 * g);
-      vf = gload8(p.v + krow * p.ldv + h * D + 8 * g);
-    }
-    for (int kbk = wi; kbk < NKB; kbk += W) {
-      const bf16x8 kc = kf, vc = vf;
-      if (kbk + W < NKB) {
-        const int64_t krow = fb + (kbk + W) * 16 + li;
-        kf = gload8(p.k + krow * p.ldk + h * D + 8 * g);
-        vf = gload8(p.v + krow * p.ldv + h * D + 8 * g);
-      }
-      const int key = kbk * 16 + li;
-      const int ck = kb[key] - boff(p);   // bin(q, key) = kb[q] - ck
-      f32x4 dk[DB], dv[DB];
-#pragma unroll
-      for (int d = 0; d < DB; ++d) { dk[d] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[d] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-      for (int qc = 0; qc < L; qc += 32) {
-        f32x4 sa[2], da[2];
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-          sa[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Qimg, qc + 16 * bi, lane), kc,
-                                                           f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          da[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Dimg, qc + 16 * bi, lane), vc,
-                                                           f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        }
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-          const int q0 = qc + 16 * bi + 4 * g;
-          const f32x4 lv = *(const f32x4*)(ls + q0);
-          const f32x4 dlq = *(const f32x4*)(dls + q0);
-          const float* up = ub + (kb_fast(kbf, q0) - ck);   // up[r] = ub[bin(q0 + r, key)]
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = sa[bi][r] * sc2 + up[r];
-            const float pr = fexp2(x - lv[r]);
-            const float ds = pr * (da[bi][r] - dlq[r]);
-            sa[bi][r] = pr;
-            da[bi][r] = ds;   // the score scale is applied once per dK output below (exact for 8)
-          }
-        }
-        const bf16x8 pa = pack_perm(sa[0], sa[1]);
-        const bf16x8 dsa = pack_perm(da[0], da[1]);
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-          dv[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, trfrag_sw(Dimg, qc, d * 16, lane), dv[d], 0, 0, 0);
-          dk[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa, trfrag_sw(Qimg, qc, d * 16, lane), dk[d], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < DB; ++d) dk[d] *= p.scale;
-      // C[key][d]: rows = keys kbk*16 + 4g + r, col = d*16 + li
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = fb + kbk * 16 + 4 * g + r;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-          p.dk[row * p.lddk + h * D + d * 16 + li] = f2bf(dk[d][r]);
-          p.dv[row * p.lddv + h * D + d * 16 + li] = f2bf(dv[d][r]);
-        }
-      }
-    }
-  }
-}
-#undef CT_DKV_LOAD
 
 // --------------------------- backward dK dV, biased, base spatial shape, LDS-DMA staged (round 5)
-// attn_bwd_dkv_persist_kernel with the next frame's Q / dO images landing in a second LDS buffer by
-// LDS-DMA (6 x 1 KB per wave, the dQ kernel's swizzled 64-B rows) instead of through 6 x 16 B of
-// staging registers per thread: at the 168-VGPR cap of 12 waves those registers went to scratch
-// right after their loads (112 B per lane), so every frame's staging latency was paid in full.
-// The frame's lse / delta still come through registers (2 floats per thread) into one LDS copy,
+// attn_bwd_dkv_kernel<32, true, 12, true> made persistent over frames (r02): 32 workgroups per
+// head walk frames s = blockIdx.x / H, + gridDim.x / H, ... with their head's bias table loaded
+// once (the per-pair kernel pays every (frame, head) pair's staging latency with nothing to
+// overlap it: 1 workgroup per CU).  The NEXT frame's Q / dO images land in a second LDS buffer by
+// LDS-DMA (6 x 1 KB per wave) while this frame computes; staged through 6 x 16 B of registers per
+// thread instead, those went to scratch right after their loads at the 168-VGPR cap of 12 waves
+// (112 B per lane), so every frame's staging latency was paid in full.  The images are unpadded
+// 64-B rows with the dQ kernel's chunk swizzle (the padded 80-B rows conflict under gfx950's
+// ds_read_b128 lane groups: 35 % of the per-pair kernel's LDS cycles, r02 PMC).
+// The frame's lse / delta come through registers (2 floats per thread) into one LDS copy,
 // written between two barriers.  The K / V fragments of a wave's next key block -- the next
 // frame's first one during its last block -- are loaded one block ahead; their first use also
 // drains the DMA queue (hipcc cannot see it), which gives the next frame's images one key block
-// (of three) to land.  Same arithmetic and results as the persist kernel.
-// LDS: 2 x (Q + dO) 147,456 + lse / delta 4,608 + bias 8,848 + positions 2,304 = 163,216 B.
+// (of three) to land.  Same arithmetic as the per-pair kernel, except that each query's lse and
+// delta enter as the score / dP MFMAs' accumulator inputs (below) and the score scale is applied
+// once per dK output.
 constexpr int DKD_W = 12, DKD_NT = DKD_W * 64;
+// LDS layout, shared by the kernel and its launcher: two frame buffers of a Q and a dO image
+// (64-B rows), lse and delta of the frame, then the bias table and the query positions
+template <int LF>
+struct DkvDmaLds {
+  static constexpr int IMG = LF * 64, BUF = 2 * IMG;
+  static constexpr size_t bytes(int nbins) {
+    return (size_t)2 * BUF + 2 * LF * 4 + (size_t)((nbins + 3) & ~3) * 4 + LF * 4;
+  }
+};
+// Every shape that reaches the <576> kernel fits the 160 KiB of LDS: a bias shape has grid_h x
+// grid_w = L = 576 (fill), so nbins = (2h - 1)(2w - 1) = 2,305 - 2 (h + w) <= 2,209 (24 x 24),
+// i.e. at most 147,456 + 4,608 + 8,848 + 2,304 = 163,216 B.
+static_assert(DkvDmaLds<576>::bytes(2209) == 163216 && DkvDmaLds<576>::bytes(2209) <= 160 * 1024, "LDS budget");
 template <int LF>
 __global__ __launch_bounds__(DKD_NT) void attn_bwd_dkv_dma_kernel(AP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int D = 32, DB = 2, W = DKD_W, NTH = DKD_NT, L = LF, NKB = L / 16;
-  constexpr int IMG = L * 64, BUF = 2 * IMG, NG = BUF / 1024 / W;   // 1-KB DMA rows per wave per frame
+  constexpr int IMG = DkvDmaLds<LF>::IMG, BUF = DkvDmaLds<LF>::BUF, NG = BUF / 1024 / W;   // 1-KB DMA rows per wave per frame
   static_assert(L % 32 == 0 && BUF % (1024 * W) == 0 && IMG % (1024 * NG) == 0 && NKB >= W, "full shape");
   const int tid = threadIdx.x, lane = tid & 63, wi = tid >> 6;
   const int h = blockIdx.x % p.H, wg = blockIdx.x / p.H, nwg = gridDim.x / p.H;
@@ -1615,13 +1405,10 @@ __global__ __launch_bounds__(DKD_NT) void attn_bwd_dkv_dma_kernel(AP p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid < L) {
-#if CTCLIP_ATTN_CFOLD
+      // each query's lse and delta are folded into the MFMAs' accumulator inputs: one VALU
+      // subtraction per score and per dP less than subtracting them per element (round 5)
       ls[tid] = -lsv / p.scale;   // the score MFMA's accumulator input: sc2 (q.k - lse / scale) = x - lse
       dls[tid] = -dlv;            // the dP MFMA's: dP - delta
-#else
-      ls[tid] = lsv * LOG2E;
-      dls[tid] = dlv;
-#endif
     }
     __syncthreads();
     const int sn = s + nwg;
@@ -1648,34 +1435,21 @@ __global__ __launch_bounds__(DKD_NT) void attn_bwd_dkv_dma_kernel(AP p) {
         f32x4 sa[2], da[2];
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi) {
-#if CTCLIP_ATTN_CFOLD
           // C[q][key], register r = query q0 + r: its -lse / scale and -delta as the accumulator inputs
           const int q0 = qc + 16 * bi + 4 * g;
           const f32x4 cS = *(const f32x4*)(ls + q0), cD = *(const f32x4*)(dls + q0);
-#else
-          const f32x4 cS = f32x4{0.f, 0.f, 0.f, 0.f}, cD = cS;
-#endif
           sa[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Qimg, qc + 16 * bi, lane), kc, cS, 0, 0, 0);
           da[bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowfrag_sw(Dimg, qc + 16 * bi, lane), vc, cD, 0, 0, 0);
         }
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi) {
           const int q0 = qc + 16 * bi + 4 * g;
-#if !CTCLIP_ATTN_CFOLD
-          const f32x4 lv = *(const f32x4*)(ls + q0);
-          const f32x4 dlq = *(const f32x4*)(dls + q0);
-#endif
           const float* up = ub + (kb_fast(kbf, q0) - ck);   // up[r] = ub[bin(q0 + r, key)]
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float x = sa[bi][r] * sc2 + up[r];
-#if CTCLIP_ATTN_CFOLD
             const float pr = fexp2(x);
             const float ds = pr * da[bi][r];
-#else
-            const float pr = fexp2(x - lv[r]);
-            const float ds = pr * (da[bi][r] - dlq[r]);
-#endif
             sa[bi][r] = pr;
             da[bi][r] = ds;   // the score scale is applied once per dK output below (exact for 8)
           }
@@ -1726,8 +1500,6 @@ void set_attrs() {
   (void)hipFuncSetAttribute((const void*)attn_bwd_dq_bias_kernel<9, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024);
   (void)hipFuncSetAttribute((const void*)attn_bwd_dq_bias_dma_kernel<576>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_persist_kernel<576>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_dma_kernel<576>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1792,82 +1564,6 @@ int fill(AP& p, const ctclip_attn_args* a) {
   p.pp = pp;
   return 0;
 }
-
-// LDS bytes of the tables after the images: [BIAS: ub + kb] + madd[pp][Lp] (+ bins for dq)
-size_t table_bytes(const AP& p, int Lp, bool bins) {
-  size_t b = (size_t)p.pp * Lp * 4;
-  const size_t nb4 = (size_t)((p.nbins + 3) & ~3);
-  if (p.bias_u) b += nb4 * 4 + (size_t)Lp * 4 + (bins ? nb4 * 4 : 0);
-  return b;
-}
-
-int g_fwd_qb = 3;
-// static-bound softmax in the QB = 3 forward (ctclip_attn_set_fwd_smax): measured SLOWER at the base
-// shape, 254 vs 235 us per layer (profiles/r03d_attnsmax_ab.log) -- its per-workgroup prologue (the
-// key norms and bias-table range over 576 rows + 2,209 bins, a block reduction and a barrier for
-// each of 1,536 workgroups) costs more than the per-chunk max / rescale it removes -- so off
-int g_fwd_smax = 0;
-// the C-init score chain (attn_fwd_kernel CINIT; ctclip_attn_set_fwd_cinit(0) restores the round-5 kernel)
-int g_fwd_cinit = 1;
-
-template <int D>
-void launch_fwd(const AP& p, dim3 grid, size_t lds, hipStream_t st) {
-  if constexpr (D == 32) {
-    if (run_ok(p)) {
-      // query blocks processed together per wave (1 = the r02 kernel): ctclip_attn_set_fwd_qb
-      // (A/B, bit-identical results)
-      const int qb = g_fwd_qb;
-      if (qb == 3 && g_fwd_smax)
-        hipLaunchKernelGGL((attn_fwd_kernel<D, true, 12, true, 3, true>), grid, dim3(12 * 64), lds, st, p);
-      else if (qb == 3 && g_fwd_cinit)
-        hipLaunchKernelGGL((attn_fwd_kernel<D, true, 12, true, 3, false, true>), grid, dim3(12 * 64), lds, st, p);
-      else if (qb == 3) hipLaunchKernelGGL((attn_fwd_kernel<D, true, 12, true, 3>), grid, dim3(12 * 64), lds, st, p);
-      else if (qb == 2) hipLaunchKernelGGL((attn_fwd_kernel<D, true, 12, true, 2>), grid, dim3(12 * 64), lds, st, p);
-      else hipLaunchKernelGGL((attn_fwd_kernel<D, true, 12, true>), grid, dim3(12 * 64), lds, st, p);
-      return;
-    }
-  }
-  if (p.bias_u) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), grid, dim3(12 * 64), lds, st, p);
-  else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), grid, dim3(NT), lds, st, p);
-}
-
-template <int D>
-void launch_dq(const AP& p, dim3 grid, size_t lds, hipStream_t st) {
-  if (p.bias_u) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, true>), grid, dim3(NT), lds, st, p);
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false>), grid, dim3(NT), lds, st, p);
-}
-
-template <int D>
-void launch_dkv(const AP& p, dim3 grid, size_t lds, hipStream_t st) {
-  if constexpr (D == 32) {
-    static int persist = -1;   // CTCLIP_ATTN_DKV_PERSIST=0: the per-pair kernel (A/B)
-    if (persist < 0) { const char* e = getenv("CTCLIP_ATTN_DKV_PERSIST"); persist = e ? atoi(e) != 0 : 1; }
-    if (persist && run_ok(p) && p.L == 576 && p.s_pos == 1 && p.n_inner == 1 && p.pp == 1 && !p.kmask &&
-        p.nseq >= 2 && 256 % p.H == 0) {
-      const int per_head = std::min(p.nseq, 256 / p.H);
-      // LDS-DMA staged variant (CTCLIP_ATTN_DKV_DMA=0: the register-staged persist kernel; A/B)
-      static int dma = -1;
-      if (dma < 0) { const char* e = getenv("CTCLIP_ATTN_DKV_DMA"); dma = e ? atoi(e) != 0 : 1; }
-      const size_t lds_d = (size_t)4 * 576 * 64 + 2 * 576 * 4 + (size_t)((p.nbins + 3) & ~3) * 4 + 576 * 4;
-      if (dma && lds_d <= 160 * 1024) {
-        hipLaunchKernelGGL((attn_bwd_dkv_dma_kernel<576>), dim3(per_head * p.H), dim3(DKD_NT), lds_d, st, p);
-        return;
-      }
-      const size_t lds_p = (size_t)2 * 576 * 64 + 2 * 576 * 4 + (size_t)((p.nbins + 3) & ~3) * 4 + 576 * 4;
-      if (lds_p <= 160 * 1024) {
-        hipLaunchKernelGGL((attn_bwd_dkv_persist_kernel<576>), dim3(per_head * p.H), dim3(DKP_NT), lds_p, st, p);
-        return;
-      }
-    }
-    if (run_ok(p)) {
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, true, 12, true>), grid, dim3(12 * 64), lds, st, p);
-      return;
-    }
-  }
-  if (p.bias_u) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, true>), grid, dim3(12 * 64), lds, st, p);
-  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false>), grid, dim3(NT), lds, st, p);
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // Short sequences (L <= 32, head dim 32, no bias / key mask): the temporal transformer's
@@ -2199,6 +1895,126 @@ bool small_ok(const AP& p, int D) {
   return D == 32 && p.L <= 32 && !p.bias_u && !p.kmask && p.drop_p == 0.f && fits;
 }
 
+constexpr size_t small_bwd_lds() { return (size_t)SW * (3 * SIMG + 256); }   // attn_small_bwd_kernel's areas
+
+// ------------------------------------------------------------------------------- launch plan
+// The shape predicates (with run_ok above, each stated once):
+// the layout the <576> kernels are specialised to -- full 24 x 24-token frames, rows contiguous
+bool base_frame_ok(const AP& p) { return run_ok(p) && p.L == 576 && p.s_pos == 1 && p.n_inner == 1; }
+// the persistent dK/dV kernel also wants frames to walk and whole workgroups per head
+bool dkv_frames_ok(const AP& p) { return p.pp == 1 && !p.kmask && p.nseq >= 2 && 256 % p.H == 0; }
+// the frame-inner dQ + bias-gradient kernels: a bias gradient to bin, <= 9 key chunks per key half
+bool dq_frames_ok(const AP& p, int D) {
+  return D == 32 && p.bias_u && p.dbias_u && !p.kmask && (pad32(p.L) / 32 + 1) / 2 <= 9;
+}
+
+// The A/B environment switches that stay (their other kernel is also reached by shape), NAME=0:
+bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : true;
+}
+bool env_dkv_persist() { static const bool on = env_on("CTCLIP_ATTN_DKV_PERSIST"); return on; }   // 0: per-pair dK/dV
+bool env_dq_dma() { static const bool on = env_on("CTCLIP_ATTN_DQ_DMA"); return on; }             // 0: generic frame-inner dQ
+bool env_small_coop() { static const bool on = env_on("CTCLIP_ATTN_SMALL_COOP"); return on; }     // 0: per-wave stores
+
+// diagnostic settings of the RUN forward (ctclip_attn_set_fwd_qb / _smax / _cinit).
+// query blocks processed together per wave (1 = the r02 kernel; bit-identical results)
+int g_fwd_qb = 3;
+// static-bound softmax in the QB = 3 forward: measured SLOWER at the base shape, 254 vs 235 us per
+// layer (profiles/r03d_attnsmax_ab.log) -- its per-workgroup prologue (the key norms and bias-table
+// range over 576 rows + 2,209 bins, a block reduction and a barrier for each of 1,536 workgroups)
+// costs more than the per-chunk max / rescale it removes -- so off
+int g_fwd_smax = 0;
+// the C-init score chain (attn_fwd_kernel CINIT; 0 restores the round-5 kernel)
+int g_fwd_cinit = 1;
+
+enum class FwdK { Small, SmallCoop, Plain32, Plain64, Bias32, Bias64, Run1, Run2, Run3, Run3Smax, Run3Cinit };
+enum class DqK { Fused, Plain32, Plain64, Bias32, Bias64, Frames, FramesRun, FramesDma };   // Fused: in the small kernel
+enum class DkvK { Small, SmallCoop, Plain32, Plain64, Bias32, Bias64, Run, FramesDma };
+struct Pass {
+  dim3 grid, block;
+  size_t lds = 0;
+};
+struct Plan {
+  FwdK fwdk;
+  DqK dqk;
+  DkvK dkvk;
+  Pass fwd, dq, dkv;
+  size_t pair_lds_dq, pair_lds_dkv;   // of the per-pair backward kernels, whichever run (ctclip_attn_bwd's shape test)
+  int nqg = 0, nfc = 0;               // frame-inner dQ: query groups, frame chunks
+  bool slab = false;                  // its partial bins may go to a workspace, of ws_floats floats
+  int64_t ws_floats = 0;
+};
+
+// frame chunks of the frame-inner dQ kernels: at least two workgroups per CU, then (up to twice
+// that) the count whose last dispatch round is fullest -- 72 x 14 = 1,008 workgroups = 3.94 rounds
+// of 256 at the base shape (measured: nfc 8 / 14 / 28 -> spatial backward 1,109 / 1,074 / 1,242 us)
+int frame_chunks(const AP& p, int nqg) {
+  const int per = p.H * nqg;
+  const int lo = std::max(1, std::min(p.nseq, (2 * 256 + per - 1) / per));
+  int nfc = lo;
+  double best = 0.0;
+  for (int f = lo; f <= std::min(p.nseq, 2 * lo); ++f) {
+    const long wgs = (long)per * f, rounds = (wgs + 255) / 256;
+    const double eff = (double)wgs / (double)(rounds * 256);
+    if (eff > best + 1e-3) { best = eff; nfc = f; }
+  }
+  return nfc;
+}
+
+Plan make_plan(const AP& p, int D) {
+  Plan pl;
+  const int pairs = p.nseq * p.H;
+  const bool d32 = D == 32, bias = p.bias_u != nullptr, run = d32 && run_ok(p);
+  const Pass pair_pass{dim3(cdiv(pairs, p.pp)), dim3(bias ? 12 * 64 : NT), 0};
+  pl.pair_lds_dq = d32 ? dq_lds<32>(p) : dq_lds<64>(p);
+  pl.pair_lds_dkv = d32 ? dkv_lds<32>(p) : dkv_lds<64>(p);
+  if (small_ok(p, D)) {
+    const bool coop = env_small_coop() && p.H % SW == 0;
+    const dim3 grid(cdiv(pairs, SW)), block(SW * 64);
+    pl.fwdk = coop ? FwdK::SmallCoop : FwdK::Small;
+    pl.fwd = {grid, block, small_fwd_lds(coop)};
+    pl.dqk = DqK::Fused;
+    pl.dkvk = coop ? DkvK::SmallCoop : DkvK::Small;
+    pl.dkv = {grid, block, small_bwd_lds()};
+    return pl;
+  }
+  if (run)
+    pl.fwdk = g_fwd_qb == 3 ? (g_fwd_smax ? FwdK::Run3Smax : g_fwd_cinit ? FwdK::Run3Cinit : FwdK::Run3)
+                            : g_fwd_qb == 2 ? FwdK::Run2 : FwdK::Run1;
+  else pl.fwdk = bias ? (d32 ? FwdK::Bias32 : FwdK::Bias64) : (d32 ? FwdK::Plain32 : FwdK::Plain64);
+  pl.fwd = pair_pass;
+  pl.fwd.lds = d32 ? fwd_lds<32>(p) : fwd_lds<64>(p);
+
+  if (dq_frames_ok(p, D)) {
+    const bool dma = env_dq_dma() && base_frame_ok(p);
+    pl.nqg = cdiv(p.L, 64);
+    pl.nfc = frame_chunks(p, pl.nqg);
+    pl.dqk = dma ? DqK::FramesDma : run ? DqK::FramesRun : DqK::Frames;
+    pl.dq = {dim3(p.H, pl.nqg, pl.nfc), dim3(dma ? DQD_NT : NT), dma ? DqDmaLds<576>::bytes(p.nbins) : dq_bias_lds(p)};
+    pl.slab = (p.H * p.nbins) % 4 == 0;
+    pl.ws_floats = (int64_t)pl.nqg * pl.nfc * p.H * p.nbins;
+  } else {
+    pl.dqk = bias ? (d32 ? DqK::Bias32 : DqK::Bias64) : (d32 ? DqK::Plain32 : DqK::Plain64);
+    pl.dq = {pair_pass.grid, dim3(NT), pl.pair_lds_dq};
+  }
+
+  if (d32 && env_dkv_persist() && base_frame_ok(p) && dkv_frames_ok(p)) {
+    pl.dkvk = DkvK::FramesDma;
+    pl.dkv = {dim3(std::min(p.nseq, 256 / p.H) * p.H), dim3(DKD_NT), DkvDmaLds<576>::bytes(p.nbins)};
+  } else {
+    pl.dkvk = run ? DkvK::Run : bias ? (d32 ? DkvK::Bias32 : DkvK::Bias64) : (d32 ? DkvK::Plain32 : DkvK::Plain64);
+    pl.dkv = pair_pass;
+    pl.dkv.lds = pl.pair_lds_dkv;
+  }
+  return pl;
+}
+
+template <typename... A>
+void launch(void (*kernel)(A...), const Pass& s, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kernel, s.grid, s.block, s.lds, st, args...);
+}
+
 }  // namespace
 
 extern "C" int ctclip_attn_fwd(const ctclip_attn_args* a, void* stream) {
@@ -2206,69 +2022,34 @@ extern "C" int ctclip_attn_fwd(const ctclip_attn_args* a, void* stream) {
   int rc = fill(p, a);
   if (rc) return rc;
   if (!s_attr) { set_attrs(); s_attr = true; }
-  const int Lp = (p.L + 31) & ~31;
-  const int pairs = p.nseq * p.H;
-  if (small_ok(p, a->D)) {
-    static const int coop_env = [] { const char* e = getenv("CTCLIP_ATTN_SMALL_COOP"); return e ? atoi(e) : 1; }();
-    if (coop_env && p.H % SW == 0)   // CTCLIP_ATTN_SMALL_COOP=0: per-wave stores (A/B)
-      hipLaunchKernelGGL(attn_small_fwd_kernel<true>, dim3(cdiv(pairs, SW)), dim3(SW * 64), small_fwd_lds(true),
-                         (hipStream_t)stream, p);
-    else
-      hipLaunchKernelGGL(attn_small_fwd_kernel<false>, dim3(cdiv(pairs, SW)), dim3(SW * 64), small_fwd_lds(false),
-                         (hipStream_t)stream, p);
-    CT_CHECK_LAUNCH();
-    return 0;
+  const Plan pl = make_plan(p, a->D);
+  const Pass& f = pl.fwd;
+  hipStream_t st = (hipStream_t)stream;
+  if (f.lds > 160 * 1024) return CT_ESHAPE;
+  switch (pl.fwdk) {
+    case FwdK::Small: launch(attn_small_fwd_kernel<false>, f, st, p); break;
+    case FwdK::SmallCoop: launch(attn_small_fwd_kernel<true>, f, st, p); break;
+    case FwdK::Plain32: launch(attn_fwd_kernel<32, false>, f, st, p); break;
+    case FwdK::Plain64: launch(attn_fwd_kernel<64, false>, f, st, p); break;
+    case FwdK::Bias32: launch(attn_fwd_kernel<32, true>, f, st, p); break;
+    case FwdK::Bias64: launch(attn_fwd_kernel<64, true>, f, st, p); break;
+    case FwdK::Run1: launch(attn_fwd_kernel<32, true, 12, true>, f, st, p); break;
+    case FwdK::Run2: launch(attn_fwd_kernel<32, true, 12, true, 2>, f, st, p); break;
+    case FwdK::Run3: launch(attn_fwd_kernel<32, true, 12, true, 3>, f, st, p); break;
+    case FwdK::Run3Smax: launch(attn_fwd_kernel<32, true, 12, true, 3, true>, f, st, p); break;
+    case FwdK::Run3Cinit: launch(attn_fwd_kernel<32, true, 12, true, 3, false, true>, f, st, p); break;
   }
-  const size_t RSb = a->D * 2 + 16;
-  const size_t lds = (size_t)p.pp * 2 * Lp * RSb + table_bytes(p, Lp, false) + 256;   // + block-reduce scratch
-  if (lds > 160 * 1024) return CT_ESHAPE;
-  dim3 grid(cdiv(pairs, p.pp));
-  if (a->D == 32) launch_fwd<32>(p, grid, lds, (hipStream_t)stream);
-  else launch_fwd<64>(p, grid, lds, (hipStream_t)stream);
   CT_CHECK_LAUNCH();
   return 0;
 }
 
-// launch plan of the frame-inner dQ + bias-gradient kernels (shared with the workspace query)
-struct DqPlan {
-  int nqg = 0, nfc = 0;
-  bool dma = false;
-  size_t lds = 0, lds_dma = 0;
-};
-bool dq_plan(const AP& p, int D, DqPlan& pl) {
-  const int Lp = (p.L + 31) & ~31, nc = Lp / 32;
-  if (!(D == 32 && p.bias_u && p.dbias_u && !p.kmask && (nc + 1) / 2 <= 9)) return false;
-  const size_t RSb = D * 2 + 16;
-  pl.nqg = cdiv(p.L, 64);
-  // frame chunks: at least two workgroups per CU, then (up to twice that) the count whose last
-  // dispatch round is fullest -- 72 x 14 = 1,008 workgroups = 3.94 rounds of 256 at the base
-  // shape (measured: nfc 8 / 14 / 28 -> spatial backward 1,109 / 1,074 / 1,242 us)
-  const int per = p.H * pl.nqg;
-  const int lo = std::max(1, std::min(p.nseq, (2 * 256 + per - 1) / per));
-  pl.nfc = lo;
-  double best = 0.0;
-  for (int f = lo; f <= std::min(p.nseq, 2 * lo); ++f) {
-    const long wgs = (long)per * f, rounds = (wgs + 255) / 256;
-    const double eff = (double)wgs / (double)(rounds * 256);
-    if (eff > best + 1e-3) { best = eff; pl.nfc = f; }
-  }
-  pl.lds = (size_t)2 * Lp * RSb + 2 * (size_t)((p.nbins + 3) & ~3) * 4 + 2 * (size_t)Lp * 4 + 4 * 64 * 8 * 4;
-  static int dma_ok = -1;   // CTCLIP_ATTN_DQ_DMA=0: the generic kernel (A/B)
-  if (dma_ok < 0) { const char* e = getenv("CTCLIP_ATTN_DQ_DMA"); dma_ok = e ? atoi(e) != 0 : 1; }
-  pl.lds_dma = (size_t)2 * 2 * 576 * 64 + (size_t)((p.nbins + 3) & ~3) * 4 + 576 * 4;
-  pl.dma = dma_ok && run_ok(p) && p.L == 576 && p.s_pos == 1 && p.n_inner == 1 && p.nbins * 4 <= 2 * 576 * 64 &&
-           pl.lds_dma <= 160 * 1024;
-  return true;
-}
-
 // floats of the optional bias-gradient workspace (ctclip_attn_args.dbias_ws) for this shape;
-// 0 when the shape bins with atomics (no frame-inner dQ kernel / not the LDS-DMA one)
+// 0 when the shape bins with atomics (no frame-inner dQ kernel)
 extern "C" int ctclip_attn_bwd_ws_floats(const ctclip_attn_args* a) {
   AP p;
   if (fill(p, a)) return 0;
-  DqPlan pl;
-  if (!dq_plan(p, a->D, pl) || (pl.dma && !CTCLIP_ATTN_DIAG_BIN) || (p.H * p.nbins) % 4) return 0;
-  return pl.nqg * pl.nfc * p.H * p.nbins;
+  const Plan pl = make_plan(p, a->D);
+  return pl.slab ? (int)pl.ws_floats : 0;
 }
 
 extern "C" int ctclip_attn_bwd(const ctclip_attn_args* a, void* stream) {
@@ -2276,53 +2057,42 @@ extern "C" int ctclip_attn_bwd(const ctclip_attn_args* a, void* stream) {
   int rc = fill(p, a);
   if (rc) return rc;
   if (!s_attr) { set_attrs(); s_attr = true; }
-  const int Lp = (p.L + 31) & ~31;
-  const int pairs = p.nseq * p.H;
-  const size_t RSb = a->D * 2 + 16;
-  const size_t lds1 = (size_t)p.pp * 2 * Lp * RSb + table_bytes(p, Lp, true);
-  const size_t lds2 = (size_t)p.pp * (2 * Lp * RSb + 2 * Lp * 4) + table_bytes(p, Lp, false);
-  if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return CT_ESHAPE;
-  dim3 grid(cdiv(pairs, p.pp));
+  const Plan pl = make_plan(p, a->D);
+  // (the per-pair kernels' sizes are tested for every shape, the small ones included)
+  if (pl.pair_lds_dq > 160 * 1024 || pl.pair_lds_dkv > 160 * 1024) return CT_ESHAPE;
+  if (pl.dq.lds > 160 * 1024) return CT_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
-  if (small_ok(p, a->D)) {
-    static const int coop_env = [] { const char* e = getenv("CTCLIP_ATTN_SMALL_COOP"); return e ? atoi(e) : 1; }();
-    const size_t lds = (size_t)SW * (3 * SIMG + 256);
-    if (coop_env && p.H % SW == 0)
-      hipLaunchKernelGGL(attn_small_bwd_kernel<true>, dim3(cdiv(pairs, SW)), dim3(SW * 64), lds, st, p);
-    else
-      hipLaunchKernelGGL(attn_small_bwd_kernel<false>, dim3(cdiv(pairs, SW)), dim3(SW * 64), lds, st, p);
-    CT_CHECK_LAUNCH();
-    return 0;
+  // the frame-inner kernels' partial bins go to the workspace when the caller gave one
+  const bool slab = pl.slab && p.dbias_ws && a->dbias_ws_floats >= pl.ws_floats;
+  if (!slab) p.dbias_ws = nullptr;
+  switch (pl.dqk) {
+    case DqK::Fused: break;
+    case DqK::Plain32: launch(attn_bwd_dq_kernel<32, false>, pl.dq, st, p); break;
+    case DqK::Plain64: launch(attn_bwd_dq_kernel<64, false>, pl.dq, st, p); break;
+    case DqK::Bias32: launch(attn_bwd_dq_kernel<32, true>, pl.dq, st, p); break;
+    case DqK::Bias64: launch(attn_bwd_dq_kernel<64, true>, pl.dq, st, p); break;
+    case DqK::Frames: launch(attn_bwd_dq_bias_kernel<9>, pl.dq, st, p, pl.nfc); break;
+    case DqK::FramesRun: launch(attn_bwd_dq_bias_kernel<9, true>, pl.dq, st, p, pl.nfc); break;
+    case DqK::FramesDma: launch(attn_bwd_dq_bias_dma_kernel<576>, pl.dq, st, p, pl.nfc); break;
   }
-  DqPlan pl;
-  if (dq_plan(p, a->D, pl)) {
-    // frame-inner dQ + bias-gradient kernel (see attn_bwd_dq_bias_kernel)
-    const int nqg = pl.nqg, nfc = pl.nfc;
-    if (pl.lds > 160 * 1024) return CT_ESHAPE;
-    const bool slab = (CTCLIP_ATTN_DIAG_BIN || !pl.dma) && p.dbias_ws && (p.H * p.nbins) % 4 == 0 &&
-                      a->dbias_ws_floats >= (int64_t)nqg * nfc * p.H * p.nbins;
-    if (!slab) p.dbias_ws = nullptr;
-    if (pl.dma)
-      hipLaunchKernelGGL((attn_bwd_dq_bias_dma_kernel<576>), dim3(p.H, nqg, nfc), dim3(DQD_NT), pl.lds_dma, st, p, nfc);
-    else if (run_ok(p)) hipLaunchKernelGGL((attn_bwd_dq_bias_kernel<9, true>), dim3(p.H, nqg, nfc), dim3(NT), pl.lds, st, p, nfc);
-    else hipLaunchKernelGGL((attn_bwd_dq_bias_kernel<9>), dim3(p.H, nqg, nfc), dim3(NT), pl.lds, st, p, nfc);
+  if (pl.nfc) {
     CT_CHECK_LAUNCH();
     if (slab) {   // deterministic sum of the workgroups' partial bins into dbias_u
       // [H][nbins] summed as one row of H * nbins floats (nbins = 2,209 is odd; the product is not)
       const int64_t n = (int64_t)p.H * p.nbins;
-      const int r = ctclip_reduce_slabs(p.dbias_ws, (int64_t)nqg * nfc, 1, n, n, p.dbias_u, n, 1, 1, stream);
+      const int r = ctclip_reduce_slabs(p.dbias_ws, (int64_t)pl.nqg * pl.nfc, 1, n, n, p.dbias_u, n, 1, 1, stream);
       if (r) return r;
     }
-    launch_dkv<32>(p, grid, lds2, st);
-    CT_CHECK_LAUNCH();
-    return 0;
   }
-  if (a->D == 32) {
-    launch_dq<32>(p, grid, lds1, st);
-    launch_dkv<32>(p, grid, lds2, st);
-  } else {
-    launch_dq<64>(p, grid, lds1, st);
-    launch_dkv<64>(p, grid, lds2, st);
+  switch (pl.dkvk) {
+    case DkvK::Small: launch(attn_small_bwd_kernel<false>, pl.dkv, st, p); break;
+    case DkvK::SmallCoop: launch(attn_small_bwd_kernel<true>, pl.dkv, st, p); break;
+    case DkvK::Plain32: launch(attn_bwd_dkv_kernel<32, false>, pl.dkv, st, p); break;
+    case DkvK::Plain64: launch(attn_bwd_dkv_kernel<64, false>, pl.dkv, st, p); break;
+    case DkvK::Bias32: launch(attn_bwd_dkv_kernel<32, true>, pl.dkv, st, p); break;
+    case DkvK::Bias64: launch(attn_bwd_dkv_kernel<64, true>, pl.dkv, st, p); break;
+    case DkvK::Run: launch(attn_bwd_dkv_kernel<32, true, 12, true>, pl.dkv, st, p); break;
+    case DkvK::FramesDma: launch(attn_bwd_dkv_dma_kernel<576>, pl.dkv, st, p); break;
   }
   CT_CHECK_LAUNCH();
   return 0;
