@@ -257,7 +257,7 @@ inline int pad32(int L) { return (L + 31) & ~31; }
 // ------------------------------------------------------------------------------------ forward
 // W waves per workgroup: 12 for the spatial (BIAS) shapes, whose 36 query blocks then split
 // evenly (3 per wave) at 12 waves per CU; 8 otherwise.
-// RUN (bias shapes with Wg % 4 == 0 and L % 32 == 0): the 4 keys a lane scores per MFMA block
+// RUN (bias shapes with Wg % 4 == 0, L % 32 == 0 and no key mask, run_ok): the 4 keys a lane scores per MFMA block
 // are consecutive in one grid row, so their bins are cq - kb[k0] - 0..3 -- one table read and one
 // address for all four bias reads (fixed offsets) -- and there are no padded keys to mask.
 // QB query blocks per wave are processed TOGETHER (same key chunk loop): their score / softmax /
@@ -1517,8 +1517,10 @@ void set_attrs() {
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
-// bias shapes whose 4-key / 4-query MFMA groups never straddle a grid row and have no padding
-bool run_ok(const AP& p) { return p.bias_u && p.Wg % 4 == 0 && p.L % 32 == 0; }
+// bias shapes whose 4-key / 4-query MFMA groups never straddle a grid row and have no padding.
+// The RUN kernels have no key-validity table at all (load_tables REV, the RUN score chains), so a
+// key mask takes the general bias kernels, which add it per key.
+bool run_ok(const AP& p) { return p.bias_u && !p.kmask && p.Wg % 4 == 0 && p.L % 32 == 0; }
 
 int fill(AP& p, const ctclip_attn_args* a) {
   if (a->D != 32 && a->D != 64) return CT_ESHAPE;

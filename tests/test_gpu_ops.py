@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attn_common import _attn_ref, _cpb_table, _gather_rows
 from oracle import ctclip_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -194,37 +195,6 @@ def test_peg_x32(K, mode, shape, D):
 
 
 # ----------------------------------------------------------------------------- attention
-def _gather_rows(n_inner, s_outer, s_inner, s_pos, nseq, L):
-    s = torch.arange(nseq)[:, None]
-    i = torch.arange(L)[None, :]
-    return ((s // n_inner) * s_outer + (s % n_inner) * s_inner + i * s_pos).to(dev)
-
-
-def _attn_ref(q, k, v, rows, H, D, scale, bias=None, kmask=None):
-    nseq, L = rows.shape
-    def g(t):
-        return t[rows.reshape(-1)].reshape(nseq, L, H, D).permute(0, 2, 1, 3)
-    s = torch.einsum('shid,shjd->shij', g(q), g(k)) * scale
-    if bias is not None:
-        s = s + bias
-    if kmask is not None:
-        s = s.masked_fill(~kmask[:, None, None, :].bool(), float('-inf'))
-    a = s.softmax(-1)
-    o = torch.einsum('shij,shjd->shid', a, g(v))
-    out = torch.zeros(q.shape[0], H * D, device=dev, dtype=q.dtype)
-    out = out.index_copy(0, rows.reshape(-1), o.permute(0, 2, 1, 3).reshape(nseq * L, H * D))
-    return out
-
-
-def _cpb_table(H, gh, gw):
-    nb = (2 * gh - 1) * (2 * gw - 1)
-    u = torch.randn(H, nb, device=dev) * 0.5
-    pos = torch.stack(torch.meshgrid(torch.arange(gh), torch.arange(gw), indexing='ij')).reshape(2, -1).t()
-    rel_ = pos[:, None, :] - pos[None, :, :]
-    bins = ((rel_[..., 0] + gh - 1) * (2 * gw - 1) + (rel_[..., 1] + gw - 1)).to(dev)
-    return u, bins
-
-
 @pytest.mark.parametrize('case', ['spatial', 'spatial_small', 'spatial_8x8', 'temporal', 'temporal_l5_h3', 'temporal_l32', 'bert',
                                   'bert_leftpad'])
 def test_attention(K, case):
