@@ -166,6 +166,18 @@ class MlmMaskArgs(ctypes.Structure):
     ]
 
 
+class ProbeArgs(ctypes.Structure):
+    """ctclip_probe_args (include/ctclip_hip.h): one step of the linear-probe head."""
+    _fields_ = [
+        ('X', c_vp), ('ldx', c_i64), ('N', c_i64),
+        ('idx', c_vp),
+        ('M', c_i32), ('D', c_i32), ('P', c_i32), ('pad', c_i32),
+        ('W', c_vp), ('b', c_vp), ('Y', c_vp), ('pos_weight', c_vp),
+        ('loss', c_vp), ('dW', c_vp), ('db', c_vp), ('Z', c_vp), ('count', c_vp),
+        ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 # name -> argtypes (restype is int32 unless _RESTYPES names another)
 _SIGS = {
     'ctclip_version': [],
@@ -299,6 +311,8 @@ _SIGS = {
     'ctclip_mlm_ce_ws_bytes': [c_i32],
     'ctclip_mlm_ce': [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
     'ctclip_mlm_scatter': [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp],
+    'ctclip_probe_step': [ctypes.POINTER(ProbeArgs), c_vp],
+    'ctclip_probe_step_ws_bytes': [ctypes.POINTER(ProbeArgs)],
     'ctclip_sgemm': [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
                      c_i32, c_f32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp],
     'ctclip_embed_fwd': [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -309,7 +323,8 @@ _SIGS = {
                     c_vp, c_vp],
 }
 _RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_retrieval_ranks_ws_bytes': c_i64,
-             'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64}
+             'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64,
+             'ctclip_probe_step_ws_bytes': c_i64}
 
 
 def register(name, argtypes):

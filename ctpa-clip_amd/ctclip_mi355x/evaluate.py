@@ -49,8 +49,8 @@ def _sorted_scores(probs, labels):
     """The part of a metric call that does not depend on the resamples: argument checks, the f32
     scores [N, P] with signed zero canonicalised, the uint8 labels and the ascending order [P, N]
     (one ``torch.sort`` per label) -- made once, walked by both kernels."""
-    if probs.ndim != 2 or not probs.is_cuda:
-        raise ValueError(f'evaluate: probs must be a device tensor [N, P], got {tuple(probs.shape)} on {probs.device}')
+    if probs.ndim != 2:
+        raise ValueError(f'evaluate: probs must be a tensor [N, P], got {tuple(probs.shape)} on {probs.device}')
     N, P = probs.shape
     y = _labels_u8(labels, probs.device)
     if tuple(y.shape) != (N, P):
@@ -59,6 +59,30 @@ def _sorted_scores(probs, labels):
     s = (probs.detach().float() + 0.0).contiguous()
     order = torch.sort(s.t(), dim=1).indices.to(torch.int32).contiguous()          # [P, N], ascending
     return s, y, order
+
+
+def _auroc_host(s, y, rows):
+    """``ctclip_auroc_boot``'s count restated in torch for HOST tensors (the linear probe's CPU path and its
+    tests; device tensors always take the kernel): per (resample, label) the tie-aware Mann-Whitney count in
+    64-bit integers -- pairs (positive above negative) + half the tied pairs, doubled -- and one f64 division;
+    NaN for one class only."""
+    N, P = s.shape
+    S = rows.shape[0]
+    mult = torch.zeros(S, N, dtype=torch.int64)
+    mult.scatter_add_(1, rows.long(), torch.ones(S, N, dtype=torch.int64))
+    out = torch.empty(S, P, dtype=torch.float64)
+    for p in range(P):
+        _, inv = torch.unique(s[:, p], sorted=True, return_inverse=True)          # tie groups, ascending
+        G = int(inv.max()) + 1
+        yp = y[:, p].long()
+        pos = torch.zeros(S, G, dtype=torch.int64).index_add_(1, inv, mult * yp)
+        neg = torch.zeros(S, G, dtype=torch.int64).index_add_(1, inv, mult * (1 - yp))
+        below = torch.cumsum(neg, 1) - neg
+        u2 = (pos * (2 * below + neg)).sum(1)
+        den = 2 * pos.sum(1) * neg.sum(1)
+        out[:, p] = torch.where(den > 0, u2.double() / den.clamp(min=1).double(), torch.full((), float('nan'),
+                                                                                           dtype=torch.float64))
+    return out
 
 
 def _walk(symbol, width, sorted_scores, rows):
@@ -70,6 +94,10 @@ def _walk(symbol, width, sorted_scores, rows):
     if rows.ndim != 2 or rows.shape[1] != N:
         raise ValueError(f'evaluate: resample indices must be [S, {N}], got {tuple(rows.shape)}')
     S = rows.shape[0]
+    if not s.is_cuda:
+        if symbol != 'ctclip_auroc_boot':
+            raise ValueError(f'evaluate: {symbol} runs on device tensors only, got scores on {s.device}')
+        return _auroc_host(s, y, rows)
     out = torch.empty((S, P) + width, device=s.device, dtype=torch.float64)
     call(symbol, ptr(s), ptr(y), ptr(order), ptr(rows), N, P, S, ptr(out), stream_ptr())
     return out
@@ -92,7 +120,8 @@ def _identity(probs):
 
 def auroc(probs, labels):
     """Per-label AUROC [P] f64 (evaluate.py:160-207 ``evaluate_internal``); NaN for a label with
-    one class only.  probs: device tensor [N, P]; labels: [N, P] of 0 / 1."""
+    one class only.  probs: device tensor [N, P] (a host tensor takes ``_auroc_host``, the same integer
+    count in torch); labels: [N, P] of 0 / 1."""
     return _auroc_rows(probs, labels, _identity(probs))[0]
 
 

@@ -1269,6 +1269,74 @@ def clip_loss_tiled(t_raw, i_raw, log_temp, t_extra=None, i_extra=None, decouple
     return loss, dt, di, dtx, dix, dlt, pair
 
 
+PROBE_OUTPUTS = ('loss', 'dW', 'db', 'Z', 'count')
+
+
+def probe_step(X, W, b, Y, *, idx=None, pos_weight=None, want=('loss', 'dW', 'db'), out=None):
+    """One full-batch step of the linear-probe head (ctclip_probe_step, csrc/probe.hip): BCE-with-logits of
+    ``X[idx] @ W.T + b`` against the uint8 labels ``Y`` (255 = not labelled), mean over the counted entries,
+    and its gradient, in one pass over X.  X [N, D] f32 (row stride >= D, a multiple of 4), W [P, D], b [P],
+    Y [N, P] uint8 (None with ``want=('Z',)``), idx [M] int32 or None, pos_weight [P] or None.  Returns a dict
+    of the outputs named in ``want`` (of PROBE_OUTPUTS): loss [1], dW [P, D], db [P], Z [M, P], count int32
+    [1].  ``out``: preallocated tensors for some of them.  Nothing is read back to the host."""
+    want = tuple(want)
+    if not want or any(k not in PROBE_OUTPUTS for k in want):
+        raise ValueError(f'probe_step: want is a non-empty subset of {PROBE_OUTPUTS}, got {want}')
+    if X.dim() != 2 or W.dim() != 2 or b.dim() != 1:
+        raise ValueError(f'probe_step: X [N, D], W [P, D], b [P], got {tuple(X.shape)}, {tuple(W.shape)}, '
+                         f'{tuple(b.shape)}')
+    N, D = X.shape
+    P = W.shape[0]
+    if X.dtype != F32 or W.dtype != F32 or b.dtype != F32:
+        raise ValueError(f'probe_step: f32 X, W, b, got {X.dtype}, {W.dtype}, {b.dtype}')
+    if W.shape[1] != D or b.shape[0] != P:
+        raise ValueError(f'probe_step: W {tuple(W.shape)} / b {tuple(b.shape)} do not match X {tuple(X.shape)}')
+    if not 1 <= P <= 32 or D % 16 or not 16 <= D <= 1024:
+        raise ValueError(f'probe_step: 1 <= P <= 32, D % 16 == 0, 16 <= D <= 1024, got W {tuple(W.shape)}')
+    if not W.is_contiguous() or not b.is_contiguous():
+        raise ValueError(f'probe_step: W and b contiguous, got W strides {W.stride()}')
+    if N < 1 or X.stride(1) != 1 or X.stride(0) < D or X.stride(0) % 4 or X.data_ptr() % 16 or W.data_ptr() % 16:
+        raise ValueError(f'probe_step: X {tuple(X.shape)} strides {X.stride()}: unit column stride, row stride >= D '
+                         'and a multiple of 4, 16-byte aligned X and W')
+    stats = any(k != 'Z' for k in want)
+    if stats:
+        if Y is None or Y.dtype != torch.uint8 or tuple(Y.shape) != (N, P) or not Y.is_contiguous():
+            raise ValueError(f'probe_step: Y contiguous uint8 {(N, P)}, got '
+                             f'{None if Y is None else (Y.dtype, tuple(Y.shape))}')
+    if idx is not None:
+        if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError(f'probe_step: idx contiguous int32 [M], got {idx.dtype} {tuple(idx.shape)}')
+        M = idx.shape[0]
+    else:
+        M = N
+    if M < 1:
+        raise ValueError(f'probe_step: M >= 1 rows, got idx {tuple(idx.shape)}')
+    if pos_weight is not None and (pos_weight.dtype != F32 or tuple(pos_weight.shape) != (P,)
+                                   or not pos_weight.is_contiguous()):
+        raise ValueError(f'probe_step: pos_weight contiguous f32 [{P}], got {pos_weight.dtype} '
+                         f'{tuple(pos_weight.shape)}')
+    dev = X.device
+    shapes = dict(loss=((1,), F32), dW=((P, D), F32), db=((P,), F32), Z=((M, P), F32), count=((1,), torch.int32))
+    res = {}
+    for k in want:
+        shp, dt = shapes[k]
+        o = None if out is None else out.get(k)
+        if o is None:
+            o = torch.empty(shp, device=dev, dtype=dt)
+        elif o.dtype != dt or tuple(o.shape) != shp or not o.is_contiguous() or o.device != dev:
+            raise ValueError(f'probe_step: out[{k!r}] contiguous {dt} {shp}, got {o.dtype} {tuple(o.shape)}')
+        res[k] = o
+    a = _lib.ProbeArgs(X=ptr(X), ldx=X.stride(0), N=N, idx=ptr(idx), M=M, D=D, P=P, W=ptr(W), b=ptr(b),
+                       Y=ptr(Y) if stats else None, pos_weight=ptr(pos_weight), loss=ptr(res.get('loss')),
+                       dW=ptr(res.get('dW')), db=ptr(res.get('db')), Z=ptr(res.get('Z')), count=ptr(res.get('count')))
+    if stats:
+        nbytes = _lib.lib().ctclip_probe_step_ws_bytes(_lib.ctypes.byref(a))
+        ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=F32)
+        a.ws, a.ws_bytes = ptr(ws), nbytes
+    call('ctclip_probe_step', _lib.ctypes.byref(a), stream_ptr())
+    return res
+
+
 def zero_shot(t_raw, i_raw, log_temp):
     """Raw prompt latents [2P, Dl] (pairs present / not present) x raw image latents [N, Dl] ->
     (probs [N, P], scores [N, P, 2]); ct_clip/ctclip_inference.py:305-315."""

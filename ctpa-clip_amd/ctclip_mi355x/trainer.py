@@ -471,6 +471,36 @@ class CTClipTrainer:
             return classifier.attribute(volumes, **kw)
         return self._eval_pass('attribute', 'attribution', run)
 
+    def linear_probe(self, train_volumes, train_labels, volumes, labels, *, n_boot=0, curves=False, batch_size=8,
+                     **fit_kw):
+        """Linear-probe evaluation between steps: fit a ``probe.LinearProbe`` (one logistic head per
+        pathology, ``fit_kw`` to ``LinearProbe.fit``) on the frozen image latents of ``train_volumes`` /
+        ``train_labels`` and score it on ``volumes`` / ``labels``.  Returns
+        ``probe.LinearProbeEvaluator.evaluate``'s dict -- the keys of ``validate`` -- plus ``probe`` (the
+        fitted head) and ``fit_loss`` (the per-step loss, on the device).  The number of labels is
+        ``train_labels.shape[1]``.
+
+        The contract is ``validate``'s: ``flush()`` first, a codebook EMA still pending afterwards raises, the
+        forwards run in eval mode under ``no_grad``, the status word is saved, cleared, read and restored
+        around the pass, ``EvalGuardError`` if the pass set any bit (e.g. a non-finite volume), the training
+        mode restored.  No tower weight changes.  With world > 1 every rank calls it at the same step; each
+        rank fits on what it was passed, and the pass adds no collective."""
+        from .probe import LinearProbeEvaluator, NonFiniteLossError
+
+        def run():
+            ev = LinearProbeEvaluator(self.model, pathologies=range(torch.as_tensor(train_labels).shape[1]))
+            try:
+                fit_loss = ev.fit(train_volumes, train_labels, batch_size=batch_size, **fit_kw)
+            except NonFiniteLossError:
+                # a flagged training volume (e.g. NaN voxels) is the cause, not the fit: EvalGuardError names it
+                if self._guard and int(K.status_word(self.device).item()):
+                    return None
+                raise
+            res = ev.evaluate(volumes, labels, n_boot=n_boot, curves=curves, batch_size=batch_size)
+            res['probe'], res['fit_loss'] = ev.probe, fit_loss
+            return res
+        return self._eval_pass('linear_probe', 'linear probe', run)
+
     def _eval_pass(self, method, what, run):
         """``run()`` as an evaluation pass between steps (``validate`` has the contract)."""
         self.flush()

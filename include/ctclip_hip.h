@@ -914,6 +914,37 @@ int ctclip_mlm_ce(float* logits, void* dlogits_bf16, int64_t ld, const int32_t* 
 int ctclip_mlm_scatter(const float* dsel, int64_t lds, const int32_t* sel, int32_t M, int32_t D, float* dh,
                        int64_t ldh, int64_t R, void* stream);
 
+/* ---------------------------------------------------------------- linear probe (csrc/probe.hip)
+ * One full-batch step of a multi-label logistic head over frozen f32 latents: BCE-with-logits (torch's
+ * stable formula with pos_weight) forward and gradient in ONE pass over X, both products exact f32 on the
+ * matrix pipe, no float atomics, bit-reproducible (two launches: row tiles -> one slab per workgroup, then a
+ * fixed-order slab sum).
+ *   z = x . w^T + b;  L = 1 + (pos_weight - 1) y;  l = (1 - y) z + L (max(-z, 0) + log1p(exp(-|z|)))
+ *   r = (1 - y) - L (1 - sigmoid(z));  loss = sum l / count;  dW = r^T X / count;  db = sum_rows r / count
+ * over the COUNTED entries: label 0 / 1 (255 = not labelled: no loss, no gradient, not counted) of a row
+ * the step runs over.  count == 0: loss 0, gradients 0.
+ * X [N][ldx] f32 (ldx >= D, ldx % 4 == 0, 16-B aligned); idx [M] int32 or NULL: the step runs over rows
+ * X[idx[m]] (repeats allowed; an index outside [0, N) is a row of zeros that counts nothing), NULL needs
+ * M == N; W [P][D] f32 contiguous, 16-B aligned; b [P]; Y [N][P] uint8, indexed by the same row as X;
+ * pos_weight [P] or NULL (ones).  Outputs, each optional (NULL = not computed; at least one): loss [1], dW [P][D],
+ * db [P], Z [M][P] (logits; Z alone is the predict path: one launch, Y / ws unused), count int32 [1].
+ * ws: ctclip_probe_step_ws_bytes(a) bytes (a function of M, D, P alone; 0 = unsupported shape), 16-B
+ * aligned, needed unless Z is the only output.  1 <= P <= 32, 16 <= D <= 1024, D % 16 == 0, M >= 1:
+ * CT_ESHAPE otherwise; a missing pointer, idx NULL with M != N or a short ws: CT_EINVAL; CT_EALIGN. */
+typedef struct {
+  const float* X; int64_t ldx; int64_t N;
+  const int32_t* idx;
+  int32_t M, D, P, pad;
+  const float* W; const float* b;
+  const uint8_t* Y;
+  const float* pos_weight;
+  float* loss; float* dW; float* db; float* Z;
+  int32_t* count;
+  void* ws; int64_t ws_bytes;
+} ctclip_probe_args;
+int ctclip_probe_step(const ctclip_probe_args* a, void* stream);
+int64_t ctclip_probe_step_ws_bytes(const ctclip_probe_args* a);
+
 #ifdef __cplusplus
 }
 #endif
