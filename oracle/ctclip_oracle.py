@@ -144,7 +144,7 @@ def cpb_rel_pos(h, w):
 def cpb_forward(sd, p, h, w, layers=2):
     """``ContinuousPositionBias.forward`` (``ct_clip/attention.py:257-276``): MLP over the
     relative positions in fp32, LeakyReLU(0.1) between layers, output (heads, i, j)."""
-    x = cpb_rel_pos(h, w).to(torch.float32)
+    x = cpb_rel_pos(h, w).to(sd[f'{p}net.0.0.weight'].dtype)     # fp32; float64 when the weights are
     for li in range(layers):
         x = F.leaky_relu(F.linear(x, sd[f'{p}net.{li}.0.weight'], sd[f'{p}net.{li}.0.bias']), 0.1)
     x = F.linear(x, sd[f'{p}net.{layers}.weight'], sd[f'{p}net.{layers}.bias'])
@@ -241,7 +241,7 @@ def vq_forward(x, embed, cluster_size, training, decay=0.8, force_ind=None):
       the old code); straight-through estimator x + (q - x).detach().
     PARITY UNPINNED beyond the argmax: see module docstring."""
     shape = x.shape
-    flat = F.normalize(x.reshape(-1, shape[-1]).float(), dim=-1)
+    flat = F.normalize(x.reshape(-1, shape[-1]).to(embed.dtype), dim=-1)   # fp32 (float64 audits: the codebook's)
     emb = embed.reshape(-1, shape[-1])
     dist = flat @ emb.t()
     ind = dist.argmax(dim=-1) if force_ind is None else force_ind.reshape(-1).to(torch.int64)
@@ -292,7 +292,14 @@ def ctvit_decode(sd, p, tokens, cfg: ViTConfig):
     bias = cpb_forward(sd, p + 'spatial_rel_pos_bias.', h, w, cfg.cpb_layers)
     x = transformer_forward(sd, p + 'enc_spatial_transformer.', x, cfg.spatial_depth, cfg.heads,
                             cfg.dim_head, video_shape, bias)
-    y = F.linear(x.reshape(b, t, h, w, d), sd[p + 'to_pixels.0.weight'], sd[p + 'to_pixels.0.bias'])
+    return to_pixels(sd, p, x.reshape(b, t, h, w, d), cfg)
+
+
+def to_pixels(sd, p, x, cfg: ViTConfig):
+    """``CTViT.to_pixels`` (``ct_clip/ctvit.py:194-197``) on decoded tokens x (b, t, h, w, d): the last
+    step of ``ctvit_decode``."""
+    b, t, h, w, d = x.shape
+    y = F.linear(x, sd[p + 'to_pixels.0.weight'], sd[p + 'to_pixels.0.bias'])
     c, pt, ps = cfg.channels, cfg.temporal_patch_size, cfg.patch_size
     y = y.reshape(b, t, h, w, c, pt, ps, ps).permute(0, 4, 1, 5, 2, 6, 3, 7)
     return y.reshape(b, c, t * pt, h * ps, w * ps)
@@ -308,35 +315,50 @@ def ctvit_recon(sd, p, video, cfg: ViTConfig, training, force_ind=None):
 
 
 # ----------------------------------------------------------------------------- BERT
-def bert_forward(sd, p, ids, mask, cfg: BertConfig):
-    """BERT-base encoder as called at ``ct_clip/ct_clip.py:685-686`` (third-party
-    ``transformers.BertModel``; restated: post-LN, GELU-erf, additive -inf-style mask,
-    dropout 0).  Returns last_hidden_state (b, L, hidden)."""
-    b, L = ids.shape
+def bert_embed(sd, p, ids, cfg: BertConfig):
+    """``BertEmbeddings``: word + token_type(0) + position, LayerNorm; (b, L) ids -> (b, L, hidden)."""
+    L = ids.shape[1]
     pos = torch.arange(L)
     # padding_idx: the pad id's row takes part in the forward but gets no gradient
     x = F.embedding(ids, sd[p + 'embeddings.word_embeddings.weight'], padding_idx=cfg.pad_id) \
         + sd[p + 'embeddings.token_type_embeddings.weight'][0] \
         + sd[p + 'embeddings.position_embeddings.weight'][pos]
-    x = _ln(x, sd[p + 'embeddings.LayerNorm.weight'], sd[p + 'embeddings.LayerNorm.bias'], cfg.eps)
-    nh, hd = cfg.heads, cfg.hidden // cfg.heads
-    add_mask = (1.0 - mask.to(torch.float32))[:, None, None, :] * torch.finfo(torch.float32).min
-    for i in range(cfg.layers):
-        lp = f'{p}encoder.layer.{i}.'
+    return _ln(x, sd[p + 'embeddings.LayerNorm.weight'], sd[p + 'embeddings.LayerNorm.bias'], cfg.eps)
 
-        def lin(t, name):
-            return F.linear(t, sd[lp + name + '.weight'], sd[lp + name + '.bias'])
-        q = lin(x, 'attention.self.query').reshape(b, L, nh, hd).transpose(1, 2)
-        k = lin(x, 'attention.self.key').reshape(b, L, nh, hd).transpose(1, 2)
-        v = lin(x, 'attention.self.value').reshape(b, L, nh, hd).transpose(1, 2)
-        s = (q @ k.transpose(-1, -2)) / math.sqrt(hd) + add_mask
-        a = s.softmax(-1) @ v
-        a = a.transpose(1, 2).reshape(b, L, cfg.hidden)
-        x = _ln(lin(a, 'attention.output.dense') + x, sd[lp + 'attention.output.LayerNorm.weight'],
-                sd[lp + 'attention.output.LayerNorm.bias'], cfg.eps)
-        hmid = F.gelu(lin(x, 'intermediate.dense'))
-        x = _ln(lin(hmid, 'output.dense') + x, sd[lp + 'output.LayerNorm.weight'],
-                sd[lp + 'output.LayerNorm.bias'], cfg.eps)
+
+def bert_add_mask(mask):
+    """The additive key mask of ``BertModel`` (b, 1, 1, L): 0 on tokens, finfo(float32).min on pads."""
+    return (1.0 - mask.to(torch.float32))[:, None, None, :] * torch.finfo(torch.float32).min
+
+
+def bert_layer(sd, lp, x, add_mask, cfg: BertConfig):
+    """One ``BertLayer`` (post-LN, GELU-erf, dropout 0) on x (b, L, hidden); ``lp`` its key prefix."""
+    b, L, _ = x.shape
+    nh, hd = cfg.heads, cfg.hidden // cfg.heads
+
+    def lin(t, name):
+        return F.linear(t, sd[lp + name + '.weight'], sd[lp + name + '.bias'])
+    q = lin(x, 'attention.self.query').reshape(b, L, nh, hd).transpose(1, 2)
+    k = lin(x, 'attention.self.key').reshape(b, L, nh, hd).transpose(1, 2)
+    v = lin(x, 'attention.self.value').reshape(b, L, nh, hd).transpose(1, 2)
+    s = (q @ k.transpose(-1, -2)) / math.sqrt(hd) + add_mask
+    a = s.softmax(-1) @ v
+    a = a.transpose(1, 2).reshape(b, L, cfg.hidden)
+    x = _ln(lin(a, 'attention.output.dense') + x, sd[lp + 'attention.output.LayerNorm.weight'],
+            sd[lp + 'attention.output.LayerNorm.bias'], cfg.eps)
+    hmid = F.gelu(lin(x, 'intermediate.dense'))
+    return _ln(lin(hmid, 'output.dense') + x, sd[lp + 'output.LayerNorm.weight'],
+               sd[lp + 'output.LayerNorm.bias'], cfg.eps)
+
+
+def bert_forward(sd, p, ids, mask, cfg: BertConfig):
+    """BERT-base encoder as called at ``ct_clip/ct_clip.py:685-686`` (third-party
+    ``transformers.BertModel``; restated: post-LN, GELU-erf, additive -inf-style mask,
+    dropout 0).  Returns last_hidden_state (b, L, hidden)."""
+    x = bert_embed(sd, p, ids, cfg)
+    add_mask = bert_add_mask(mask)
+    for i in range(cfg.layers):
+        x = bert_layer(sd, f'{p}encoder.layer.{i}.', x, add_mask, cfg)
     return x
 
 
