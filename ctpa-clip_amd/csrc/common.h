@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <type_traits>
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -61,6 +62,18 @@ __device__ __forceinline__ s16x4 ds_read_tr16_b64_asm(const void* p) {
 
 // error codes returned by the C-ABI besides hipError_t values
 enum { CT_EINVAL = 1001, CT_EALIGN = 1002, CT_ESHAPE = 1003 };
+
+// ctclip_gemm_args.act (include/ctclip_hip.h; kernels.py carries the same names)
+constexpr int ACT_NONE = 0, ACT_GELU = 1, ACT_GEGLU = 2, ACT_ARGMAX = 3, ACT_GEGLU_BWD = 4, ACT_L2N = 5,
+              ACT_GELU_BWD = 6;
+
+// The four (A, B) operand layouts as compile-time flags: f(AK, BKC) is called with
+// std::bool_constant arguments, so a generic lambda can name a kernel template with them.
+template <class F>
+static inline int by_layout(bool a_kcontig, bool b_kcontig, F&& f) {
+  if (a_kcontig) return b_kcontig ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  return b_kcontig ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
 
 __device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ u16 f2bf(float f) {

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
   __syncthreads();
 
   const int t = threadIdx.x;
-  if (p.act == 3) {
+  if (p.act == ACT_ARGMAX) {
     // argmax over this tile's columns per row: write (value, index) pairs per (row, tile)
     // C = float2 [M][ntiles]; columns >= N excluded.
     // one (value, index) per (row, 64-column group), first-max tie-break (torch.argmax semantics)
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
     return;
   }
   const bool slab = p.split_k > 1;
-  if (p.act == 4) {
+  if (p.act == ACT_GEGLU_BWD) {
     // GEGLU backward fused into dg = dy . W2 (see gemm256.hip): 8 g-columns per thread
     for (int it = 0; it < (BM * BN / 8) / NTH; ++it) {
       const int c = t + NTH * it;
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
       const u16* hr = (const u16*)p.R + bidx * p.sR + gm * p.ldr + tg * 64 + cw;
       u16* dr = (u16*)p.C + bidx * p.sC + gm * p.ldc + tg * 64 + cw;
       float x[8], gt[8], ox[8], og[8];
-      if (p.r_f16) {   // fp16 h: the derivative form [gelu(gate) | x gelu'(gate)] (gemm256.hip EP 2)
+      if (p.r_f16) {   // fp16 h: the derivative form [gelu(gate) | x gelu'(gate)] (gemm256.hip EP_TR_GEGLU)
         unpack8h(*(const u32x4*)hr, x);
         unpack8h(*(const u32x4*)(hr + 32), gt);
 #pragma unroll
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] += p.bias[gn + j];
     }
-    if (p.act == 6) {
+    if (p.act == ACT_GELU_BWD) {
       // GELU backward: C = acc * gelu'(R) with R the bf16 pre-activation (the act-1 C2), replacing
       // a bf16 dX GEMM + ctclip_gelu_bwd (one rounding fewer: acc is not rounded to bf16 first)
       float rr[8];
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
         for (int j = 0; j < 8; ++j) v[j] += rr[j];
       }
     }
-    if (p.act == 1) {
+    if (p.act == ACT_GELU) {
       // C2 (if given) keeps the pre-activation for the GELU backward
       if (p.C2) *(u32x4*)(p.C2 + bidx * p.sC2 + gm * p.ldc2 + gn) = pack8(v);
 #pragma unroll
@@ -315,11 +315,11 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
         for (int j = 0; j < 8; ++j) v[j] += rr[j];
       }
       // the fp16 GEGLU GEMM (act 2) writes h (fp16, derivative form) in the GEGLU pass below
-      if (!(H16 && p.act == 2)) *(u32x4*)Cb = pack8(v);
+      if (!(H16 && p.act == ACT_GEGLU)) *(u32x4*)Cb = pack8(v);
     }
-    if (p.C2 && p.act == 0) *(u32x4*)(p.C2 + bidx * p.sC2 + gm * p.ldc2 + gn) = pack8(v);
+    if (p.C2 && p.act == ACT_NONE) *(u32x4*)(p.C2 + bidx * p.sC2 + gm * p.ldc2 + gn) = pack8(v);
   }
-  if (p.act == 2 && p.C2) {
+  if (p.act == ACT_GEGLU && p.C2) {
     // GEGLU: each 64-column group is [32 x | 32 gate] -> 32 output columns
     for (int it = 0; it < (BM * 64 / 8) / NTH; ++it) {
       const int c = t + NTH * it;
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
       float v[8];
       if (H16) {
         // fp16 h in the derivative form [gelu(gate) | x gelu'(gate)] (the GEGLU backward's two
-        // factors; gemm256.hip EP 2), g and the factors from the fp16-rounded x / gate
+        // factors; gemm256.hip EP_TR_GEGLU), g and the factors from the fp16-rounded x / gate
         float av[8], bv[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -363,6 +363,9 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kernel(P p) {
 
 template <bool AK, bool BK, bool H16 = false>
 int launch(const P& p, int batch, hipStream_t st) {
+  static const bool attr = hipFuncSetAttribute((const void*)gemm_kernel<AK, BK, H16>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES) == hipSuccess;
+  (void)attr;
   dim3 grid(cdiv(p.N, BN), cdiv(p.M, BM), batch * p.split_k);
   hipLaunchKernelGGL((gemm_kernel<AK, BK, H16>), grid, dim3(NTH), SMEM_BYTES, st, p);
   CT_CHECK_LAUNCH();
@@ -494,7 +497,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_ep_kernel(const float* __res
       for (int j = 0; j < 8; ++j) v[j] += rr[j];
     }
   }
-  if (p.act == 1) {
+  if (p.act == ACT_GELU) {
     if (p.C2) *(u32x4*)(p.C2 + r * p.ldc2 + c) = pack8(v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = gelu_erf(v[j]);
@@ -518,10 +521,19 @@ __global__ __launch_bounds__(256) void reduce_slabs_ep_kernel(const float* __res
     }
     *(u32x4*)Cb = pack8(v);
   }
-  if (p.C2 && p.act == 0) *(u32x4*)(p.C2 + r * p.ldc2 + c) = pack8(v);
+  if (p.C2 && p.act == ACT_NONE) *(u32x4*)(p.C2 + r * p.ldc2 + c) = pack8(v);
 }
 
-static bool s_smem_set = false;
+// The routing rule to the 256 x 256 tile (ctclip_gemm256, gemm256.hip): K in whole 64-deep steps, at
+// least one full tile each way, 160 tiles in all (batch and K slabs included) and K slabs of at least
+// 512.  B2 (two-pass hi / lo weights) and the GELU backward exist in the 128-tile kernel only (the
+// text tower).  x3 operands go there whatever the shape (ctclip_gemm below).
+bool routes_to_256(const ctclip_gemm_args* a, int split, int batch) {
+  if (a->B2 || a->act == ACT_GELU_BWD) return false;
+  const int64_t tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256) * split * batch;
+  return a->K % 64 == 0 && a->M >= 256 && a->N >= 256 && tiles256 >= 160 && (split == 1 || (a->K / split) >= 512) &&
+         (!a->bias || aligned16(a->bias));
+}
 
 }  // namespace
 
@@ -530,26 +542,26 @@ extern "C" int ctclip_gemm(const ctclip_gemm_args* a, void* stream) {
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return a->M == 0 || a->N == 0 ? 0 : CT_ESHAPE;
   const int split = a->split_k > 0 ? a->split_k : 1;
   if (split > 1 && !a->c_f32) return CT_EINVAL;
-  if (a->act == 2 && !a->C2) return CT_EINVAL;
+  if (a->act == ACT_GEGLU && !a->C2) return CT_EINVAL;
   // 16-byte alignment of every operand row / chunk
   CT_REQUIRE(aligned16(a->A) && aligned16(a->B) && aligned16(a->C), CT_EALIGN);
   CT_REQUIRE(a->lda % 8 == 0 && a->ldb % 8 == 0, CT_EALIGN);
   CT_REQUIRE(a->a_kcontig ? (a->K % 8 == 0) : (a->M % 8 == 0), CT_EALIGN);
   CT_REQUIRE(a->b_kcontig ? (a->K % 8 == 0) : (a->N % 8 == 0), CT_EALIGN);
-  if (a->act != 3) {
+  if (a->act != ACT_ARGMAX) {
     CT_REQUIRE(a->N % 8 == 0 && a->ldc % 8 == 0, CT_EALIGN);
     if (a->C2) CT_REQUIRE(aligned16(a->C2) && a->ldc2 % 8 == 0, CT_EALIGN);
     if (a->R) CT_REQUIRE(aligned16(a->R) && a->ldr % 8 == 0, CT_EALIGN);
   }
-  if (a->act == 2) CT_REQUIRE(a->N % 64 == 0 && a->ldc2 % 8 == 0, CT_ESHAPE);
-  if (a->act == 4) CT_REQUIRE(a->N % 32 == 0 && a->R && !a->r_f32 && !a->c_f32 && a->split_k <= 1, CT_EINVAL);
-  if (a->act == 6)
+  if (a->act == ACT_GEGLU) CT_REQUIRE(a->N % 64 == 0 && a->ldc2 % 8 == 0, CT_ESHAPE);
+  if (a->act == ACT_GEGLU_BWD) CT_REQUIRE(a->N % 32 == 0 && a->R && !a->r_f32 && !a->c_f32 && a->split_k <= 1, CT_EINVAL);
+  if (a->act == ACT_GELU_BWD)
     CT_REQUIRE(a->R && !a->r_f32 && !a->bias && !a->accumulate && !a->C2 && split == 1 && (a->batch <= 1), CT_EINVAL);
-  if (a->act == 5)
+  if (a->act == ACT_L2N)
     CT_REQUIRE(a->C2 && a->bias && aligned16(a->bias) && !a->R && !a->c_f32 && !a->accumulate && split == 1 &&
                    (a->batch <= 1) && a->N % 64 == 0 && a->n2 > 0 && a->n2 % 64 == 0 && a->n2 <= a->N,
                CT_EINVAL);
-  if (a->B2) CT_REQUIRE(aligned16(a->B2) && a->act != 3, CT_EINVAL);
+  if (a->B2) CT_REQUIRE(aligned16(a->B2) && a->act != ACT_ARGMAX, CT_EINVAL);
   if (a->A_lo || a->B_lo) {
     // split-fp16 x3 operands: the 8-phase kernel only (any M / N; rows past the matrix are clamped
     // loads whose results are dropped), f32 rows or the x3 GEGLU pair
@@ -557,43 +569,30 @@ extern "C" int ctclip_gemm(const ctclip_gemm_args* a, void* stream) {
                CT_EINVAL);
     CT_REQUIRE(a->a_kcontig && a->b_kcontig && !a->B2 && split == 1 && !a->accumulate && a->batch <= 1, CT_EINVAL);
     CT_REQUIRE(a->K < (int64_t)64 * 10000, CT_ESHAPE);   // K-step index 3 k + s stays < 2^15
-    if (a->act == 2)
+    if (a->act == ACT_GEGLU)
       CT_REQUIRE(!a->c_f32 && !a->R && !a->bias && a->C3 && aligned16(a->C3) && a->ldc3 % 8 == 0 &&
                      (!a->C4 || (aligned16(a->C4) && a->ldc4 % 8 == 0)),
                  CT_EINVAL);
     else
-      CT_REQUIRE(a->act == 0 && a->c_f32 && (!a->R || a->r_f32), CT_EINVAL);
+      CT_REQUIRE(a->act == ACT_NONE && a->c_f32 && (!a->R || a->r_f32), CT_EINVAL);
     return ctclip_gemm256(a, 1, 1, stream);
   }
   if (a->ab_f16)   // fp16 operands: the 3D-ViT forward GEMMs and the VQ distance GEMM (act 3, round 6;
                    // K-contiguous A and B, no split-K / B2)
-    CT_REQUIRE(a->a_kcontig && a->b_kcontig && !a->B2 && split == 1 && (a->act == 0 || a->act == 2 || a->act == 3) &&
+    CT_REQUIRE(a->a_kcontig && a->b_kcontig && !a->B2 && split == 1 && (a->act == ACT_NONE || a->act == ACT_GEGLU || a->act == ACT_ARGMAX) &&
                    !a->accumulate && (a->batch <= 1),
                CT_EINVAL);
-  if (!a->B2 && a->act != 6) {   // act 6 (GELU backward): the 128-tile kernel only (text tower)
-    const int b = a->batch > 0 ? a->batch : 1;
-    const int64_t tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256) * split * b;
-    if (a->K % 64 == 0 && a->M >= 256 && a->N >= 256 && tiles256 >= 160 && (split == 1 || (a->K / split) >= 512) &&
-        (!a->bias || aligned16(a->bias)))
-      return ctclip_gemm256(a, split, b, stream);
-  }
-  if (a->act == 5) {
+  const int batch = a->batch > 0 ? a->batch : 1;
+  if (routes_to_256(a, split, batch)) return ctclip_gemm256(a, split, batch, stream);
+  if (a->act == ACT_L2N) {
     // small shapes: the plain GEMM, then the stand-alone l2norm kernel (same rule)
     ctclip_gemm_args g = *a;
-    g.act = 0;
+    g.act = ACT_NONE;
     g.bias = nullptr;
     g.C2 = nullptr;
     const int rc = ctclip_gemm(&g, stream);
     if (rc) return rc;
     return ctclip_l2norm_scale_fwd(a->C, a->ldc, a->M, a->n2 / 32, 32, a->bias, a->C2, a->ldc2, stream);
-  }
-  if (!s_smem_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    s_smem_set = true;
   }
   P p;
   p.M = a->M; p.N = a->N; p.K = a->K;
@@ -610,19 +609,16 @@ extern "C" int ctclip_gemm(const ctclip_gemm_args* a, void* stream) {
   kper = (kper + BKT - 1) / BKT * BKT;
   p.kper = kper;
   p.r_f16 = a->r_f16;
-  const int batch = a->batch > 0 ? a->batch : 1;
   hipStream_t st = (hipStream_t)stream;
-  if (a->ab_f16) return launch<true, true, true>(p, batch, st);
-  if (a->a_kcontig && a->b_kcontig) return launch<true, true>(p, batch, st);
-  if (a->a_kcontig && !a->b_kcontig) return launch<true, false>(p, batch, st);
-  if (!a->a_kcontig && a->b_kcontig) return launch<false, true>(p, batch, st);
-  return launch<false, false>(p, batch, st);
+  if (a->ab_f16) return launch<true, true, true>(p, batch, st);   // K-contiguous A and B (checked above)
+  return by_layout(a->a_kcontig, a->b_kcontig,
+                   [&](auto AK, auto BKC) { return launch<decltype(AK)::value, decltype(BKC)::value>(p, batch, st); });
 }
 
 extern "C" int ctclip_reduce_slabs_ep(const float* slabs, int64_t nslab, int64_t rows, int64_t cols, int64_t ld,
                                       const ctclip_gemm_args* a, void* stream) {
   if (rows == 0 || cols == 0) return 0;
-  CT_REQUIRE(a && (a->act == 0 || a->act == 1), CT_EINVAL);
+  CT_REQUIRE(a && (a->act == ACT_NONE || a->act == ACT_GELU), CT_EINVAL);
   CT_REQUIRE(cols % 8 == 0 && ld % 4 == 0 && a->ldc % 8 == 0 && aligned16(slabs) && aligned16(a->C), CT_EALIGN);
   if (a->bias) CT_REQUIRE(aligned16(a->bias), CT_EALIGN);
   if (a->R) CT_REQUIRE(aligned16(a->R) && a->ldr % 8 == 0, CT_EALIGN);
@@ -645,7 +641,7 @@ extern "C" int ctclip_reduce_slabs_ep(const float* slabs, int64_t nslab, int64_t
 extern "C" int ctclip_reduce_slabs_ep_drop(const float* slabs, int64_t nslab, int64_t rows, int64_t cols, int64_t ld,
                                            const ctclip_gemm_args* a, float dp, uint64_t seed, void* stream) {
   if (rows == 0 || cols == 0) return 0;
-  CT_REQUIRE(a && a->act == 0 && !a->accumulate && a->ldc == cols && dp >= 0.f && dp < 1.f, CT_EINVAL);
+  CT_REQUIRE(a && a->act == ACT_NONE && !a->accumulate && a->ldc == cols && dp >= 0.f && dp < 1.f, CT_EINVAL);
   CT_REQUIRE(cols % 8 == 0 && ld % 4 == 0 && aligned16(slabs) && aligned16(a->C), CT_EALIGN);
   if (a->bias) CT_REQUIRE(aligned16(a->bias), CT_EALIGN);
   if (a->R) CT_REQUIRE(aligned16(a->R) && a->ldr % 8 == 0, CT_EALIGN);

@@ -17,16 +17,15 @@
 
 namespace g256 {
 
-// Two shapes of one kernel template, WR = wave rows of 128:
-//   WR = 2: 256 x 256 tile, 8 waves, 4-slot ring (128 KB LDS, 1 workgroup per CU);
-//   WR = 1: 128 x 256 tile, 4 waves, 3-slot ring (72 KB LDS, 2 workgroups per CU), so one
-//           workgroup's epilogue stores drain while the other one's MFMAs run.
+// The old kernel (gemm256_kernel, ctclip_gemm_set_variant(1)): 128 x 256 x 32 tile, 4 waves, 3-slot
+// ring (72 KB LDS, 2 workgroups per CU), so one workgroup's epilogue stores drain while the other
+// one's MFMAs run.
 constexpr int BN = 256, BK = 32;
 constexpr int EP_LD = 68;                    // f32 staging row stride (64 cols + pad)
-template <int WR> struct Cfg {
-  static constexpr int BM = 128 * WR, NTH = 256 * WR;
+struct Cfg {
+  static constexpr int BM = 128, NTH = 256;
   static constexpr int ABYTES = BM * BK * 2, BBYTES = BN * BK * 2, STAGE = ABYTES + BBYTES;
-  static constexpr int NSTAGE = WR == 2 ? 4 : 3;
+  static constexpr int NSTAGE = 3;
   static constexpr int SMEM = NSTAGE * STAGE;
   static constexpr int GA = ABYTES / 16 / NTH, GB = BBYTES / 16 / NTH, G = GA + GB;   // glds per thread per tile
 };
@@ -50,24 +49,25 @@ struct P {
   int gz;        // batch * split_k (8-phase tile count = ceil(N/256) * ceil(M/256) * gz)
   int persist;   // 8-phase: persistent workgroups (one per CU) walking the tile sequence
   int pre1;      // 8-phase TR: the next tile's whole K-step 1 staged before the epilogue (the persistent walk)
-  // LayerNorm epilogues (EP -6 forward, -7 backward; ctclip_gemm_ln)
+  // LayerNorm epilogues (EP_LN_FWD, EP_LN_BWD; ctclip_gemm_ln)
   const float* ln_gamma; const float* ln_beta; float ln_eps;
-  u16* ln_y; int64_t ln_ldy;         // -6: LN output (bf16)
-  float* ln_mean; float* ln_rstd;    // -6: written; -7: read
-  const u16* ln_x; int64_t ln_ldx;   // -7: the LN input (bf16)
-  float* ln_pg; float* ln_pb;        // -7: [M / 128][N] column partials (dgamma, dbeta)
+  u16* ln_y; int64_t ln_ldy;         // FWD: LN output (bf16)
+  float* ln_mean; float* ln_rstd;    // FWD: written; BWD: read
+  const u16* ln_x; int64_t ln_ldx;   // BWD: the LN input (bf16)
+  float* ln_pg; float* ln_pb;        // BWD: [M / 128][N] column partials (dgamma, dbeta)
   unsigned long long* xchg;          // [2 tiles][M][2] {epoch, value} granules
   unsigned epoch;
   int* status;
   unsigned spin_limit;               // polls before giving up on the partner (status = 1)
   int ln_debug;                      // test knob: tile 1 of row block 0 never publishes
   int epi_lds;                       // transposed bf16 / GEGLU epilogues: lane-contiguous stores via LDS
-  // EP 8 (ctclip_gemm_qkv_lnfold): columns < nfold carry the LayerNorm fold
+  // EP_TR_QKV_LNFOLD (ctclip_gemm_qkv_lnfold): columns < nfold carry the LayerNorm fold
   //   C = rstd[row] * (acc - mean[row] * fold_cs[col])   (ln_mean / ln_rstd read)
   const float* fold_cs;
   int nfold;
-  // fp16 (round 5): h16 = FF1's h is fp16 -- written by the GEGLU epilogue of the fp16 kernel (EP 2,
-  // H16), read by the GEGLU backward (EP 4); ln_y16 = optional fp16 copy of the -6 LayerNorm output
+  // fp16 (round 5): h16 = FF1's h is fp16 -- written by the GEGLU epilogue of the fp16 kernel
+  // (EP_TR_GEGLU, H16), read by the GEGLU backward (EP_GEGLU_BWD_ROWS); ln_y16 = optional fp16 copy of the
+  // EP_LN_FWD LayerNorm output
   int h16;
   u16* ln_y16;
   // split-fp16 "x3" GEMM (round 6, ctclip_gemm_args.A_lo / B_lo): A = Ah + Al, B = Bh + Bl as fp16
@@ -81,8 +81,28 @@ struct P {
   u16* C3; int64_t ldc3;
   u16* C4; int64_t ldc4;
   int x3;
-  int c_col0;    // EP 6 / 8: first C column stored (ctclip_gemm_qkv_lnfold2; 0 = all)
+  int c_col0;    // EP_TR_L2N / EP_TR_QKV_LNFOLD: first C column stored (ctclip_gemm_qkv_lnfold2; 0 = all)
 };
+
+// Epilogue kind, the EP template argument of gemm8p_kernel: one kernel instantiation each, so the
+// accumulator registers never share a kernel with another epilogue's live ranges.  Negative =
+// rows staged through LDS and written as 16-B row chunks (epilogue, epilogue_ln); non-negative =
+// the transposed accumulator (MFMA operands swapped) stored without staging (epilogue_t).
+constexpr int EP_ROWS = -1;             // bias / residual / GELU / f32 or 16-bit / accumulate / bf16 copy
+constexpr int EP_ROWS_RES = -2;         // f32 rows + f32 residual (+ bias, bf16 copy), nothing else
+constexpr int EP_ARGMAX_ROWS = -3;      // (value, index) per row and 64-column group, from staged rows
+constexpr int EP_SLABS = -5;            // split-K f32 slabs: alpha only
+constexpr int EP_LN_FWD = -6;           // + residual, then LayerNorm of the row (ctclip_gemm_ln mode 1)
+constexpr int EP_LN_BWD = -7;           // LayerNorm backward of the row + residual (ctclip_gemm_ln mode 2)
+constexpr int EP_LNFOLD_BWD = -8;       // EP_ROWS_RES - c1[row] - beta[row] X (ctclip_gemm_lnfold_bwd)
+constexpr int EP_TR = 0;                // 16-bit output: bias / GELU / bf16 copy
+constexpr int EP_TR_GEGLU = 2;          // GEGLU in 32-column pairs: h (C) and g (C2)
+constexpr int EP_TR_ARGMAX = 3;         // the argmax from the accumulator registers
+constexpr int EP_TR_L2N = 6;            // 16-bit output + per-head l2norm * scale into C2 (act 5)
+constexpr int EP_TR_QKV_LNFOLD = 8;     // EP_TR_L2N with the LayerNorm fold on columns < nfold
+constexpr int EP_TR_RELAY = 10;         // EP_TR, its stores re-laid through LDS (store_blk_bf16_lds)
+constexpr int EP_TR_GEGLU_RELAY = 12;   // EP_TR_GEGLU, likewise
+constexpr int EP_GEGLU_BWD_ROWS = 14;   // GEGLU backward, h loads and dh stores row-contiguous through LDS
 
 __device__ __forceinline__ int mn_swz(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
 
@@ -154,14 +174,14 @@ __device__ __forceinline__ void xcd_remap(int& tx, int& ty) {
 // acc[i][j] is the 16x16 block (i, j) of that region in the MFMA 16x16 C layout.  Stages each
 // 32-row quarter through a wave-private LDS region (8.7 KB per wave) and writes 16-B row chunks.
 // LM (compile time, one kernel instantiation each so only that path's registers are allocated):
-// -1 = general (bias / residual / GELU / f32 or bf16 / accumulate / shadow; GEGLU), -3 = argmax,
-// -5 = split-K slabs
-template <int LM = -1>
+// EP_ROWS = general (bias / residual / GELU / f32 or bf16 / accumulate / shadow; in the old kernel
+// also GEGLU, argmax and slabs, chosen at run time), EP_ROWS_RES, EP_ARGMAX_ROWS, EP_SLABS, EP_LNFOLD_BWD
+template <int LM = EP_ROWS>
 __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* smem, int w, int wr, int wc, int lane,
                                          int64_t m0, int64_t n0, int split, int bidx) {
   float* cs = (float*)(smem + w * (32 * EP_LD * 4));   // 8.7 KB per wave, 8 waves = 70 KB
   const int64_t wrow0 = m0 + wr * 128, wcol0 = n0 + wc * 64;
-  const bool slab = LM == -5 || (LM == -1 && p.split_k > 1);
+  const bool slab = LM == EP_SLABS || (LM == EP_ROWS && p.split_k > 1);
 #pragma unroll
   for (int quarter = 0; quarter < 4; ++quarter) {
 #pragma unroll
@@ -174,7 +194,7 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
     // wave-private region: no block barrier needed, only LDS write->read ordering in the wave
     __builtin_amdgcn_s_waitcnt(0xC07F);
     const int64_t rbase = wrow0 + quarter * 32;
-    if (LM == -3 || (LM == -1 && p.act == 3)) {   // (LM -2 never takes the argmax / GEGLU paths)
+    if (LM == EP_ARGMAX_ROWS || (LM == EP_ROWS && p.act == ACT_ARGMAX)) {   // (EP_ROWS_RES never takes the argmax / GEGLU paths)
       // argmax over this wave's 64 columns: 2 lanes per row (32 columns each), (value, index)
       // per (row, 64-col group), first-max tie-break
       // (+ the group's second-best score into the optional f32 C2, see gemm.hip)
@@ -200,7 +220,7 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
         out[gm * p.ldc + (wcol0 >> 6)] = make_float2(best, __int_as_float((int)(wcol0 + bi)));
         if (p.C2) ((float*)p.C2)[bidx * p.sC2 + gm * p.ldc2 + (wcol0 >> 6)] = second;
       }
-    } else if (LM == -1 && p.act == 2) {
+    } else if (LM == EP_ROWS && p.act == ACT_GEGLU) {
       // GEGLU pairs of 32 columns: [x | gate] -> 32 outputs; h (C) keeps both halves
       for (int it = 0; it < 4; ++it) {
         const int c = lane + 64 * it;          // 256 chunks of 8 = 32 rows x 8
@@ -235,13 +255,13 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
       // four row chunks, so the bias is loaded once.
       const int64_t gn = wcol0 + (lane & 7) * 8;
       const int cc = (lane & 7) * 8;
-      const bool pre_acc = LM == -1 && !p.R && p.accumulate;
-      if constexpr (LM == -2 || LM == -8) {
+      const bool pre_acc = LM == EP_ROWS && !p.R && p.accumulate;
+      if constexpr (LM == EP_ROWS_RES || LM == EP_LNFOLD_BWD) {
         // residual mode: C (f32) = alpha acc + bias + R (f32), bf16 shadow into C2 when given
         // unconditional loads (rows / columns clamped into the matrix, results of clamped
         // chunks unused): a load under a branch must complete before its phi copy, which put a
         // vmcnt(0) behind every pair
-        // LM -8 (ctclip_gemm_lnfold_bwd): also - c1[row] - beta[row] * X[row][col] (X bf16 in
+        // EP_LNFOLD_BWD (ctclip_gemm_lnfold_bwd): also - c1[row] - beta[row] * X[row][col] (X bf16 in
         // ln_x, c1 / beta in ln_mean / ln_rstd): the folded LayerNorm backward
         f32x4 ra[4], rb[4];
         const int64_t gnc = min(gn, p.N - 8);
@@ -252,7 +272,7 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
           ra[it] = *(const f32x4*)Rp;
           rb[it] = *(const f32x4*)(Rp + 4);
         }
-        if constexpr (LM == -8) {
+        if constexpr (LM == EP_LNFOLD_BWD) {
 #pragma unroll
           for (int it = 0; it < 4; ++it) {
             const int64_t gm = min(rbase + ((lane + 64 * it) >> 3), p.M - 1);
@@ -334,7 +354,7 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
         const int64_t gm = rbase + row;
         ra[it] = rb[it] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (slab || gm >= p.M || gn >= p.N) continue;
-        if (LM == -1 && p.R) {
+        if (LM == EP_ROWS && p.R) {
           if (p.r_f32) {
             const float* Rp = (const float*)p.R + bidx * p.sR + gm * p.ldr + gn;
             ra[it] = *(const f32x4*)Rp;
@@ -386,7 +406,7 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
             for (int j = 0; j < 8; ++j) v[j] += rr[j];
           }
         }
-        if (p.act == 1) {
+        if (p.act == ACT_GELU) {
           if (p.C2) *(u32x4*)(p.C2 + bidx * p.sC2 + gm * p.ldc2 + gn) = pack8(v);
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = gelu_erf(v[j]);
@@ -411,7 +431,7 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
           }
           *(u32x4*)Cb = pack8(v);
         }
-        if (p.C2 && p.act == 0) *(u32x4*)(p.C2 + bidx * p.sC2 + gm * p.ldc2 + gn) = pack8(v);
+        if (p.C2 && p.act == ACT_NONE) *(u32x4*)(p.C2 + bidx * p.sC2 + gm * p.ldc2 + gn) = pack8(v);
       }
       }
     }
@@ -419,9 +439,9 @@ __device__ __forceinline__ void epilogue(const P& p, f32x4 (&acc)[8][4], char* s
   }
 }
 
-template <int WR, bool AK, bool BKC>
-__global__ __launch_bounds__(Cfg<WR>::NTH, 2 / WR) void gemm256_kernel(P p) {
-  using C = Cfg<WR>;
+template <bool AK, bool BKC>
+__global__ __launch_bounds__(Cfg::NTH, 2) void gemm256_kernel(P p) {
+  using C = Cfg;
   constexpr int NSTAGE = C::NSTAGE, STAGE = C::STAGE, G = C::G;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 2, wc = w & 3;
@@ -446,7 +466,7 @@ __global__ __launch_bounds__(Cfg<WR>::NTH, 2 / WR) void gemm256_kernel(P p) {
   // a raw s_barrier publishes the landed tile (a __syncthreads fence would drain every glds).
   // The slot refilled at step kt held tile kt - 1, which every wave finished before the barrier.
   const int nk = (kend > kbeg && !(p.debug & 2)) ? (int)((kend - kbeg) / BK) : 0;
-  // the first dispatch round holds two workgroups per CU (WR = 1); delaying the second one
+  // the first dispatch round holds two workgroups per CU; delaying the second one
   // offsets their store-heavy epilogues against each other's MFMA main loops
   if (p.stagger > 0) {
     const int lin = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -462,14 +482,8 @@ __global__ __launch_bounds__(Cfg<WR>::NTH, 2 / WR) void gemm256_kernel(P p) {
   };
   for (int t = 0; t < NSTAGE - 1 && t < nk; ++t) stage(t);
   for (int kt = 0; kt < nk; ++kt) {
-    if constexpr (NSTAGE == 4) {
-      if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
-      else if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (kt + NSTAGE - 1 < nk) stage(kt + NSTAGE - 1);
@@ -705,8 +719,8 @@ __device__ __forceinline__ void store_blk_bf16_lds(char* scr, u16* C, int64_t ld
 }
 
 // MODE (compile time, so each variant's row loop stays small enough to unroll fully and the
-// accumulator never leaves registers): 0 = general (bias / residual / GELU / f32 or bf16 /
-// accumulate / shadow), 2 = GEGLU, 3 = argmax, 4 = GEGLU backward, 5 = split-K slab.
+// accumulator never leaves registers): EP_TR = general (bias / residual / GELU / f32 or bf16 /
+// accumulate / shadow), EP_TR_GEGLU, EP_TR_ARGMAX, EP_TR_L2N, EP_TR_QKV_LNFOLD.
 // (the xor16 / xor32 exchanges below are ds_bpermute shuffles: permlane swaps measured 2 % slower on
 // the VQ argmax GEMM, 1.193 vs 1.171-1.176 ms, profiles/r02aw_*)
 
@@ -717,14 +731,14 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
   const int64_t wrow0 = m0 + wr * 128, wcol0 = n0 + wc * 64;
   const int64_t cl = wcol0 + 4 * g;          // this lane's column in block j: cl + 16 j
   float bias[4][4];
-  // EP 8: this wave's columns are LayerNorm-folded (wave-uniform); bias[][] then holds fold_cs
-  const bool fold = MODE == 8 && wcol0 < p.nfold;
+  // QKV_LNFOLD: this wave's columns are LayerNorm-folded (wave-uniform); bias[][] then holds fold_cs
+  const bool fold = MODE == EP_TR_QKV_LNFOLD && wcol0 < p.nfold;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (MODE == 8) {
+    if (MODE == EP_TR_QKV_LNFOLD) {
       if (fold) b = *(const f32x4*)(p.fold_cs + cl + 16 * j);
-    } else if (p.bias && p.split_k <= 1 && p.act != 3 && p.act != 5 && cl + 16 * j < p.N) b = *(const f32x4*)(p.bias + cl + 16 * j);
+    } else if (p.bias && p.split_k <= 1 && p.act != ACT_ARGMAX && p.act != ACT_L2N && cl + 16 * j < p.N) b = *(const f32x4*)(p.bias + cl + 16 * j);
 #pragma unroll
     for (int r = 0; r < 4; ++r) bias[j][r] = b[r];
   }
@@ -737,7 +751,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[j][r] = acc[i][j][r] * p.alpha;
-    if constexpr (MODE == 3) {
+    if constexpr (MODE == EP_TR_ARGMAX) {
       // argmax over the wave's 64 columns of row gm (first-max tie-break): 16 values per lane,
       // then across the 4 lanes g = 0..3 that hold the same row
       // branch-free (selects): the if / else form compiled to exec-mask branches per element and
@@ -776,7 +790,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
       }
       continue;
     }
-    if constexpr (MODE == 8) {
+    if constexpr (MODE == EP_TR_QKV_LNFOLD) {
       // LayerNorm folded into the projection (ctclip_gemm_qkv_lnfold): LN(x) W^T =
       // rstd (x (gamma o W)^T - mean (W gamma)), gamma o W pre-packed, W gamma = fold_cs
       if (fold) {
@@ -788,10 +802,10 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
           for (int r = 0; r < 4; ++r) v[j][r] = rs * (v[j][r] - mu * bias[j][r]);
       }
     }
-    if constexpr (MODE == 6 || MODE == 8) {
+    if constexpr (MODE == EP_TR_L2N || MODE == EP_TR_QKV_LNFOLD) {
       // C = bf16 result; C2 = its l2norm over each 32-column head (the wave's 64 columns are two
       // heads) times the head-dim scale p.bias[c % 32], bit-identical to ctclip_l2norm_scale_fwd
-      // (EP 8: p.bias holds two 32-scales, the folded columns' then the rest's):
+      // (QKV_LNFOLD: p.bias holds two 32-scales, the folded columns' then the rest's):
       // the permlane16 pair swap leaves each lane 8 consecutive columns (a chunk: offset
       // pair_coff(g)), summed in that kernel's order, then combined chunk 0+1, 2+3 (lanes g ^ 2)
       // and the two pairs (g ^ 1), as its xor-1 / xor-2 shuffles over the 4 lanes of a head
@@ -800,11 +814,11 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) qb[j][r] = bf2f(f2bf(v[j][r]));
-      // (EP 8: columns below c_col0 -- q, k in the eval forward, round 6 -- only feed the l2norm)
+      // (QKV_LNFOLD: columns below c_col0 -- q, k in the eval forward, round 6 -- only feed the l2norm)
       store_row_bf16((u16*)p.C + bidx * p.sC + gm * p.ldc + wcol0, v, g, rok && wcol0 >= p.c_col0, wcol0, p.N);
       if (wcol0 < p.n2) {
         const int d0 = pair_coff(g);
-        const float* sp = p.bias + d0 + (MODE == 8 && !fold ? 32 : 0);   // EP 8: the second scale set
+        const float* sp = p.bias + d0 + (MODE == EP_TR_QKV_LNFOLD && !fold ? 32 : 0);   // the second scale set
         const f32x4 s0v = *(const f32x4*)sp, s1v = *(const f32x4*)(sp + 4);
 #pragma unroll
         for (int jp = 0; jp < 2; ++jp) {
@@ -831,14 +845,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
       }
       continue;
     }
-    if constexpr (MODE == 5) {
-      float* Cf = (float*)p.C + (int64_t)split * p.M * p.ldc + bidx * p.sC + gm * p.ldc + cl;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (rok && cl + 16 * j < p.N) *(f32x4*)(Cf + 16 * j) = f32x4{v[j][0], v[j][1], v[j][2], v[j][3]};
-      continue;
-    }
-    if constexpr (MODE == 2) {
+    if constexpr (MODE == EP_TR_GEGLU) {
       // GEGLU in 32-column pairs: blocks 0,1 = x, blocks 2,3 = gate; h keeps both halves
       if constexpr (LDS) {
         const int64_t gm0 = wrow0 + i * 16;
@@ -923,7 +930,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
       }
       continue;
     }
-    if constexpr (MODE != 0) continue;
+    if constexpr (MODE != EP_TR) continue;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -950,7 +957,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
           }
       }
     }
-    if (p.act == 1) {
+    if (p.act == ACT_GELU) {
       if (p.C2) store_row_bf16(p.C2 + bidx * p.sC2 + gm * p.ldc2 + wcol0, v, g, rok, wcol0, p.N);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -989,7 +996,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
         store_row_bf16(Cb, v, g, rok, wcol0, p.N, p.epi_lds == 3);
       }
     }
-    if (p.C2 && p.act == 0) {
+    if (p.C2 && p.act == ACT_NONE) {
       if constexpr (LDS) {
         const int64_t gm0 = wrow0 + i * 16;
         store_blk_bf16_lds(scr, p.C2 + bidx * p.sC2 + gm0 * p.ldc2 + wcol0, p.ldc2, gm0, p.M, wcol0, p.N, v, g, m,
@@ -1001,7 +1008,7 @@ __device__ __forceinline__ void epilogue_t(const P& p, f32x4 (&acc)[8][4], int w
   }
 }
 
-// GEGLU backward fused into dg = dy . W2 (TR layout, EP 14): the accumulator is dg over g-space
+// GEGLU backward fused into dg = dy . W2 (TR layout, EP_GEGLU_BWD_ROWS): the accumulator is dg over g-space
 // columns; block pair (0,1) is 32-group t0 = wcol0 / 32, pair (2,3) group t0 + 1.  dg is rounded to
 // bf16 (as the stand-alone geglu_bwd reads it) and permlane-paired so every lane owns 8 consecutive
 // g-columns.  A lane of the transposed layout owns one row (lane & 15), so a 16-B load of h or store of
@@ -1112,10 +1119,10 @@ __device__ __forceinline__ void epilogue_geglu_bwd_rows(const P& p, f32x4 (&acc)
 // MI355X_MICROARCH.md § visibility, R2) and polls the partner's with relaxed agent-scope loads
 // (sc1, bypassing L1; bounded: a timeout sets *status and continues).  Both tiles combine the two
 // halves with symmetric formulas, so the two halves of a row see bit-identical statistics.
-//   MODE 6 (forward): v = alpha acc + bias + R -> C (f32) and C2 (bf16); per-row (mean, M2) merged
+//   EP_LN_FWD: v = alpha acc + bias + R -> C (f32) and C2 (bf16); per-row (mean, M2) merged
 //     pairwise at equal counts (Chan et al.), y = (v - mean) rstd gamma + beta -> ln_y (bf16);
 //     tile 0 writes mean / rstd.  Replaces residual GEMM + ln_fwd_kernel.
-//   MODE 7 (backward): dy = bf16(alpha acc) (what the unfused GEMM stored), xh = (x - mean) rstd,
+//   EP_LN_BWD: dy = bf16(alpha acc) (what the unfused GEMM stored), xh = (x - mean) rstd,
 //     g = dy gamma; the row sums of g and g xh are exchanged; C = rstd (g - mean(g) - xh mean(g xh))
 //     + R, C2 = bf16(C); per 128-row block the column sums of dy xh / dy -> ln_pg / ln_pb.  Replaces
 //     the GEMM + ln_bwd_kernel pair (same arithmetic, the sums in another order).
@@ -1150,13 +1157,13 @@ __device__ __forceinline__ void epilogue_ln(const P& p, f32x4 (&acc)[8][4], char
   {
     const f32x4 a = *(const f32x4*)(p.ln_gamma + gn), b = *(const f32x4*)(p.ln_gamma + gn + 4);
     f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f}, d = c;
-    if (MODE == 6 && p.ln_beta) { c = *(const f32x4*)(p.ln_beta + gn); d = *(const f32x4*)(p.ln_beta + gn + 4); }
+    if (MODE == EP_LN_FWD && p.ln_beta) { c = *(const f32x4*)(p.ln_beta + gn); d = *(const f32x4*)(p.ln_beta + gn + 4); }
 #pragma unroll
     for (int j = 0; j < 4; ++j) { gam[j] = a[j]; gam[4 + j] = b[j]; bet[j] = c[j]; bet[4 + j] = d[j]; }
   }
   f32x4 b0 = f32x4{0.f, 0.f, 0.f, 0.f}, b1 = b0;
-  if (MODE == 6 && p.bias) { b0 = *(const f32x4*)(p.bias + gn); b1 = *(const f32x4*)(p.bias + gn + 4); }
-  float keep[4][4][8];        // MODE 6: v per quarter / row chunk
+  if (MODE == EP_LN_FWD && p.bias) { b0 = *(const f32x4*)(p.bias + gn); b1 = *(const f32x4*)(p.bias + gn + 4); }
+  float keep[4][4][8];        // FWD: v per quarter / row chunk
   float pg[8], pb[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { pg[j] = 0.f; pb[j] = 0.f; }
@@ -1173,7 +1180,7 @@ __device__ __forceinline__ void epilogue_ln(const P& p, f32x4 (&acc)[8][4], char
           cs[(i * 16 + (lane >> 4) * 4 + r) * EP_LD + j * 16 + (lane & 15)] = acc[quarter * 2 + i][j][r];
     __builtin_amdgcn_s_waitcnt(0xC07F);
     const int64_t rbase = wrow0 + quarter * 32;
-    if constexpr (MODE == 6) {
+    if constexpr (MODE == EP_LN_FWD) {
       f32x4 ra[4], rb[4];
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
@@ -1266,7 +1273,7 @@ __device__ __forceinline__ void epilogue_ln(const P& p, f32x4 (&acc)[8][4], char
       const int r = lane + 64 * h;
       const float2 s0 = st[(wr * 128 + r) * 4 + 0], s1 = st[(wr * 128 + r) * 4 + 1];
       const float2 s2 = st[(wr * 128 + r) * 4 + 2], s3 = st[(wr * 128 + r) * 4 + 3];
-      if constexpr (MODE == 6) {
+      if constexpr (MODE == EP_LN_FWD) {
         float m = s0.x, M2 = s0.y, mm = s2.x, MM = s2.y;
         chan(m, M2, s1.x, s1.y, 32.f);
         chan(mm, MM, s3.x, s3.y, 32.f);
@@ -1306,7 +1313,7 @@ __device__ __forceinline__ void epilogue_ln(const P& p, f32x4 (&acc)[8][4], char
       const int r = lane + 64 * h;
       const float o0 = __uint_as_float((unsigned)q[h][0]), o1 = __uint_as_float((unsigned)q[h][1]);
       float2 f;
-      if constexpr (MODE == 6) {
+      if constexpr (MODE == EP_LN_FWD) {
         float m = a0[h], M2 = a1[h];
         chan(m, M2, o0, o1, 128.f);
         const float rstd = rsqrtf(M2 * (1.f / 512.f) + p.ln_eps);
@@ -1333,7 +1340,7 @@ __device__ __forceinline__ void epilogue_ln(const P& p, f32x4 (&acc)[8][4], char
   for (int quarter = 0; quarter < 4; ++quarter) {
     __builtin_amdgcn_sched_barrier(0);
     const int64_t rbase = frow0 - rl + quarter * 32;
-    if constexpr (MODE == 6) {
+    if constexpr (MODE == EP_LN_FWD) {
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const float2 f = fin[wr * 128 + quarter * 32 + it * 8 + rl];
@@ -1386,7 +1393,7 @@ __device__ __forceinline__ void epilogue_ln(const P& p, f32x4 (&acc)[8][4], char
       }
     }
   }
-  if constexpr (MODE == 7) {
+  if constexpr (MODE == EP_LN_BWD) {
     // column partials of this wave's 128 rows (lanes of equal lane & 7 hold the same columns),
     // one slab row per 128-row block
 #pragma unroll
@@ -1561,19 +1568,19 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
   stage(A0, 1); stage(B0, 1);
   wait_ahead(T.nk > 1);
 
-  // TR epilogues without the LDS relay (EP 10 / 12 use O's A1 / B1 halves as scratch) leave buffer O
+  // TR epilogues without the LDS relay (the RELAY ones use O's A1 / B1 halves as scratch) leave buffer O
   // idle, so with p.pre1 the next tile's K-step 1 is staged whole before the epilogue: its A1 / B1
   // halves get the epilogue's duration to land instead of the three MFMA phases of K-step 0 (the
   // first two K-steps of a tile ran at ~3x the steady-state time, r02 stamps).  Older loads only
   // complete earlier, so the vmcnt(4) waits of the loop stay exact.
-  // Enabled for the VQ argmax GEMM (EP 3), the GEGLU backward (EP 4 / 14) and the NN dX GEMMs (EP 0 with
-  // an N-contiguous B): 1.098 -> 1.013, 0.446 -> 0.436 and 0.313 -> 0.304 ms against the previous
+  // Enabled for the VQ argmax GEMM (EP_TR_ARGMAX), the GEGLU backward (EP_GEGLU_BWD_ROWS) and the NN dX
+  // GEMMs (EP_TR with an N-contiguous B): 1.098 -> 1.013, 0.446 -> 0.436 and 0.313 -> 0.304 ms against the previous
   // build (profiles/r04r_gemm_pre1_ab.log).  Most of the VQ gain is the compiled code rather than
   // the prefetch (spills 18 -> 14; with p.pre1 = 0 the same build runs 1.02 ms, r04s_gemm_pre1_ab.log);
   // end to end within noise (r04s_pre1_ab_bench.log).  Skipping the re-issue costs the NT plain /
   // GEGLU / l2norm kernels 4-18 spilled VGPRs (FF1 +3 %, Q / KV +7 %), and re-issuing instead
   // gains nothing, so those keep the in-loop staging.
-  constexpr bool PRE_OK = TR && (EP == 3 || EP == 14 || (EP == 0 && !BKC));
+  constexpr bool PRE_OK = TR && (EP == EP_TR_ARGMAX || EP == EP_GEGLU_BWD_ROWS || (EP == EP_TR && !BKC));
   bool pre = false;
   while (true) {
     const int nk = T.nk;
@@ -1627,25 +1634,25 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
       for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    } else if constexpr (EP == 2 || EP == 12) {
-      epilogue_t<2, EP == 12, H16, X3>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
-    } else if constexpr (EP == 14) {
+    } else if constexpr (EP == EP_TR_GEGLU || EP == EP_TR_GEGLU_RELAY) {
+      epilogue_t<EP_TR_GEGLU, EP == EP_TR_GEGLU_RELAY, H16, X3>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
+    } else if constexpr (EP == EP_GEGLU_BWD_ROWS) {
       epilogue_geglu_bwd_rows(p, acc, wr, wc, lane, T.m0, T.n0, T.bidx, smem + 2 * TILEB + wu * GB_STRIP);
-    } else if constexpr (EP == 0 || EP == 10) {
-      epilogue_t<0, EP == 10>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
-    } else if constexpr (EP == 3) {
-      epilogue_t<3>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
-    } else if constexpr (EP == 6) {
-      epilogue_t<6>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
-    } else if constexpr (EP == 8) {
-      epilogue_t<8>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
-    } else if constexpr (EP == -8) {
-      epilogue<-8>(p, acc, smem + TILEB, w, wr, wc, lane, T.m0, T.n0, T.split, T.bidx);
-    } else if constexpr (EP == -6 || EP == -7) {
-      epilogue_ln<EP == -6 ? 6 : 7>(p, acc, smem, w, wr, wc, lane, T.m0, T.n0);
+    } else if constexpr (EP == EP_TR || EP == EP_TR_RELAY) {
+      epilogue_t<EP_TR, EP == EP_TR_RELAY>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
+    } else if constexpr (EP == EP_TR_ARGMAX) {
+      epilogue_t<EP_TR_ARGMAX>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
+    } else if constexpr (EP == EP_TR_L2N) {
+      epilogue_t<EP_TR_L2N>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
+    } else if constexpr (EP == EP_TR_QKV_LNFOLD) {
+      epilogue_t<EP_TR_QKV_LNFOLD>(p, acc, wr, wc, lane, T.m0, T.n0, T.split, T.bidx, scr);
+    } else if constexpr (EP == EP_LNFOLD_BWD) {
+      epilogue<EP_LNFOLD_BWD>(p, acc, smem + TILEB, w, wr, wc, lane, T.m0, T.n0, T.split, T.bidx);
+    } else if constexpr (EP == EP_LN_FWD || EP == EP_LN_BWD) {
+      epilogue_ln<EP>(p, acc, smem, w, wr, wc, lane, T.m0, T.n0);
     } else {
       // staging in buffer O and beyond (the next tile's tile 0 is landing in E)
-      epilogue<EP == -2 || EP == -3 || EP == -5 ? EP : -1>(p, acc, smem + TILEB, w, wr, wc, lane, T.m0, T.n0, T.split, T.bidx);
+      epilogue<EP == EP_ROWS_RES || EP == EP_ARGMAX_ROWS || EP == EP_SLABS ? EP : EP_ROWS>(p, acc, smem + TILEB, w, wr, wc, lane, T.m0, T.n0, T.split, T.bidx);
     }
     if (!more) break;
     T = tile_at<X3>(p, lin, gx, gy, ntiles);
@@ -1661,168 +1668,188 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(P p) {
   }
 }
 
-// persistent grid cap (workgroups; default 256 = one per CU): lets two GEMMs on two streams share
-// the chip (ctclip_gemm_set_grid_cap)
-static int g_grid_cap = 0;
-
-template <bool AK, bool BKC, int EP, bool H16 = false, bool X3 = false>
-int launch8(const P& p, int batch, hipStream_t st) {
-  constexpr int smem = EP == -6 || EP == -7 ? SMEM_LN : EP == 14 ? SMEM_GB : p8::SMEM_P;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm8p_kernel<AK, BKC, EP, H16, X3>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr = true;
-  }
-  const int64_t ntiles = cdiv(p.N, p8::BNN) * cdiv(p.M, p8::BM) * (int64_t)p.gz;
-  if (p.persist) {
-    const int64_t cap = g_grid_cap > 0 && g_grid_cap < 256 ? g_grid_cap : 256;
-    dim3 grid((unsigned)(ntiles < cap ? ntiles : cap));
-    P q = p;
-    q.pre1 = 1;
-    hipLaunchKernelGGL((gemm8p_kernel<AK, BKC, EP, H16, X3>), grid, dim3(p8::NTH), smem, st, q);
-  } else {
-    dim3 grid(cdiv(p.N, p8::BNN), cdiv(p.M, p8::BM), batch * p.split_k);
-    hipLaunchKernelGGL((gemm8p_kernel<AK, BKC, EP, H16, X3>), grid, dim3(p8::NTH), smem, st, p);
-  }
-  CT_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int WR, bool AK, bool BKC>
-int launch(const P& p, int batch, hipStream_t st) {
-  using C = Cfg<WR>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<WR, AK, BKC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              C::SMEM);
-    attr = true;
-  }
-  dim3 grid(cdiv(p.N, BN), cdiv(p.M, C::BM), batch * p.split_k);
-  hipLaunchKernelGGL((gemm256_kernel<WR, AK, BKC>), grid, dim3(C::NTH), C::SMEM, st, p);
-  CT_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int WR>
-int launch_any(const P& p, bool ak, bool bk, int batch, hipStream_t st) {
-  if (ak && bk) return launch<WR, true, true>(p, batch, st);
-  if (ak) return launch<WR, true, false>(p, batch, st);
-  if (bk) return launch<WR, false, true>(p, batch, st);
-  return launch<WR, false, false>(p, batch, st);
-}
-
-// kernel variant: 8 = 8-phase 256 x 256 x 64 (default), 1 = 128 x 256 x 32 (2 WG/CU),
-// 2 = 256 x 256 x 32 4-slot ring.  ctclip_gemm_set_variant() selects it.
-static int g_variant = 8;
+// ---- host side: settings, the launch plan, the kernel table, the entry points ----
+static int g_variant = 8;     // 8 = the 8-phase kernel (default), 1 = the old 128 x 256 x 32 one (ctclip_gemm_set_variant)
 static int g_stagger8 = -1;   // 8-phase start stagger (units of s_sleep(32)); -1 = default
 static int g_persist = 1;     // 8-phase persistent tile loop (ctclip_gemm_set_persist)
 static int g_epi_lds = 0;     // transposed bf16 / GEGLU epilogues through LDS (ctclip_gemm_set_epi_lds)
-int variant() { return g_variant; }
-int tile_rows() { return variant() == 2 ? 2 : 1; }
+static int g_grid_cap = 0;    // persistent grid cap in workgroups, 0 = 256, one per CU (ctclip_gemm_set_grid_cap)
 
-// epilogue kind, one kernel instantiation each (so the accumulator registers never share a
-// kernel with another epilogue's live ranges): -1 = LDS-staged rows (f32 / residual / argmax /
-// split-K slabs), 0 = transposed bf16, 2 = transposed GEGLU, 4 = transposed GEGLU backward,
-// 10 / 12 = 0 / 2 with their bf16 stores re-laid through LDS (store_blk_bf16_lds), 14 = the GEGLU
-// backward, its h loads and dh stores row-contiguous through LDS (epilogue_geglu_bwd_rows)
+constexpr int EP_BY_ARGS = 1;   // make_plan: the epilogue follows from the arguments (ctclip_gemm256)
+
+struct Plan {
+  int rc;                  // 0, or the code returned instead of a launch
+  bool eight;              // kernel family: gemm8p_kernel, else gemm256_kernel
+  int ep; bool h16, x3;    // gemm8p_kernel's EP and operand format
+  int kstep; int64_t kper; // K depth of one step of that family; K range of one split
+  int stagger, pre1;
+  dim3 grid;
+};
+
+// The launch plan: every rule that picks a kernel or shapes its launch, each stated once.  p is the
+// filled parameter block but for kper / stagger / pre1, which run() sets from the plan; ep_fixed is a
+// fused entry point's epilogue, or EP_BY_ARGS.
+static Plan make_plan(const P& p, bool ak, bool bk, bool h16, int ep_fixed) {
+  Plan pl{};
+  const bool by_args = ep_fixed == EP_BY_ARGS;
+  pl.h16 = h16;
+  pl.x3 = p.x3 != 0;
+  // 8-phase whatever the variant: the fused entry points, fp16 operands, and the two epilogues that
+  // only this kernel has
+  pl.eight = g_variant == 8 || !by_args || h16 || p.act == ACT_GEGLU_BWD || p.act == ACT_L2N;
+  pl.kstep = pl.eight ? p8::BKK : BK;
+  pl.kper = (p.K / pl.kstep + p.split_k - 1) / p.split_k * pl.kstep;
+  // Start stagger (variant 8, bf16, ctclip_gemm256 only).  r01 staggered the GEGLU GEMM, whose long
+  // epilogue (h + g stores + erf) made desynchronised CUs pay off; the round 4 sweep
+  // (profiles/r04a_stagger.log, interleaved rounds) found none best for it -- 0.4229 vs 0.4289 ms at
+  // the old default 4 -- and ~1.5 % for the GEGLU backward at 8; neutral to slightly negative on
+  // the plain / residual epilogues.
+  if (by_args && !h16 && g_variant == 8) pl.stagger = g_stagger8 >= 0 ? g_stagger8 : p.act == ACT_GEGLU_BWD ? 8 : 0;
+  pl.pre1 = pl.eight && p.persist;
+  if (!pl.eight) {
+    pl.grid = dim3(cdiv(p.N, BN), cdiv(p.M, Cfg::BM), p.gz);
+  } else if (p.persist) {
+    const int64_t ntiles = cdiv(p.N, p8::BNN) * cdiv(p.M, p8::BM) * (int64_t)p.gz;
+    const int64_t cap = g_grid_cap > 0 && g_grid_cap < 256 ? g_grid_cap : 256;
+    pl.grid = dim3((unsigned)(ntiles < cap ? ntiles : cap));
+  } else {
+    pl.grid = dim3(cdiv(p.N, p8::BNN), cdiv(p.M, p8::BM), p.gz);
+  }
+  pl.ep = ep_fixed;
+  if (!by_args) return pl;
+
+  // transposed: a 16-bit output with nothing to read back (no residual, no slabs)
+  const bool tr = !p.c_f32 && !p.R && p.split_k <= 1 && p.act != ACT_ARGMAX;
+  // f32 residual rows: C (f32) = alpha acc + bias + R (f32), the one thing EP_ROWS_RES does
+  const bool res_rows = p.R && p.r_f32 && p.c_f32 && p.act == ACT_NONE && !p.accumulate;
+  // the argmax through the transposed (LDS-free) epilogue: VQ distance GEMM 1.73 -> 1.56 ms (r02);
+  // CTCLIP_GEMM_ARGMAX_TR=0: the LDS-staged one (A/B; bf16 operands only)
+  static int am_tr = -1;
+  if (am_tr < 0) { const char* e = getenv("CTCLIP_GEMM_ARGMAX_TR"); am_tr = e ? atoi(e) != 0 : 1; }
+  // the same epilogues with lane-contiguous stores through LDS (3: direct stores with sc1, EP_TR / EP_TR_GEGLU)
+  const bool relay = !h16 && (p.epi_lds == 1 || p.epi_lds == 2);
+
+  pl.rc = CT_EINVAL;
+  // fp16 operands (the 3D-ViT forward, the VQ distance GEMM): K-contiguous A and B, forward epilogues
+  if (h16 && (!ak || !bk || p.split_k > 1 || p.act == ACT_GEGLU_BWD || p.act == ACT_L2N || p.act == ACT_GELU_BWD))
+    return pl;
+  // split-fp16 operands: the GEGLU pair epilogue, or f32 rows (bias / f32 residual / bf16 copy)
+  if (pl.x3 && !(p.act == ACT_GEGLU || (p.act == ACT_NONE && p.c_f32 && (!p.R || res_rows)))) return pl;
+  pl.rc = 0;
+  if (p.act == ACT_GEGLU_BWD) pl.ep = EP_GEGLU_BWD_ROWS;
+  else if (p.act == ACT_L2N) pl.ep = EP_TR_L2N;
+  else if (p.act == ACT_ARGMAX) pl.ep = p.split_k <= 1 && (h16 || am_tr) ? EP_TR_ARGMAX : EP_ARGMAX_ROWS;
+  else if (p.act == ACT_GEGLU && (tr || h16)) pl.ep = relay ? EP_TR_GEGLU_RELAY : EP_TR_GEGLU;   // fp16: h and g always as the pair
+  else if (tr) pl.ep = relay ? EP_TR_RELAY : EP_TR;
+  else if (p.split_k > 1) pl.ep = EP_SLABS;
+  else if (res_rows) pl.ep = EP_ROWS_RES;
+  else pl.ep = EP_ROWS;
+  return pl;
+}
+
+template <bool AK, bool BKC, int EP, bool H16, bool X3>
+int launch8(const P& p, dim3 grid, hipStream_t st) {
+  constexpr int smem = EP == EP_LN_FWD || EP == EP_LN_BWD ? SMEM_LN : EP == EP_GEGLU_BWD_ROWS ? SMEM_GB : p8::SMEM_P;
+  static const bool attr = hipFuncSetAttribute((const void*)gemm8p_kernel<AK, BKC, EP, H16, X3>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
+  (void)attr;
+  hipLaunchKernelGGL((gemm8p_kernel<AK, BKC, EP, H16, X3>), grid, dim3(p8::NTH), smem, st, p);
+  CT_CHECK_LAUNCH();
+  return 0;
+}
+
 template <bool AK, bool BKC>
-int launch8_ep(const P& p, int batch, hipStream_t st) {
-  if (p.act == 4) return launch8<AK, BKC, 14>(p, batch, st);
-  if (p.act == 5) return launch8<AK, BKC, 6>(p, batch, st);
-  const bool tr = !p.c_f32 && !p.R && p.split_k <= 1 && p.act != 3;
-  if (!tr) {
-    // the argmax through the transposed (LDS-free) epilogue: VQ distance GEMM 1.73 -> 1.56 ms (r02);
-    // CTCLIP_GEMM_ARGMAX_TR=0: the LDS-staged one (A/B)
-    static int am_tr = -1;
-    if (am_tr < 0) { const char* e = getenv("CTCLIP_GEMM_ARGMAX_TR"); am_tr = e ? atoi(e) != 0 : 1; }
-    if (p.act == 3 && am_tr && p.split_k <= 1) return launch8<AK, BKC, 3>(p, batch, st);
-    if (p.act == 3) return launch8<AK, BKC, -3>(p, batch, st);
-    if (p.split_k > 1) return launch8<AK, BKC, -5>(p, batch, st);   // slabs: alpha only
-    if (p.R && p.r_f32 && p.c_f32 && p.act == 0 && !p.accumulate) return launch8<AK, BKC, -2>(p, batch, st);
-    return launch8<AK, BKC, -1>(p, batch, st);
-  }
-  // 10 / 12: the same epilogues with lane-contiguous stores through LDS (p.epi_lds)
-  const bool relay = p.epi_lds == 1 || p.epi_lds == 2;   // 3: direct stores with sc1 (EP 0 / 2)
-  if (p.act == 2) return relay ? launch8<AK, BKC, 12>(p, batch, st) : launch8<AK, BKC, 2>(p, batch, st);
-  return relay ? launch8<AK, BKC, 10>(p, batch, st) : launch8<AK, BKC, 0>(p, batch, st);
+int launch_old(const P& p, dim3 grid, hipStream_t st) {
+  static const bool attr = hipFuncSetAttribute((const void*)gemm256_kernel<AK, BKC>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM) == hipSuccess;
+  (void)attr;
+  hipLaunchKernelGGL((gemm256_kernel<AK, BKC>), grid, dim3(Cfg::NTH), Cfg::SMEM, st, p);
+  CT_CHECK_LAUNCH();
+  return 0;
 }
 
-// fp16 operands (the 3D-ViT forward: K-contiguous A and B only): the forward epilogues -- GEGLU (h in
-// fp16), plain 16-bit / l2norm-free outputs, the LDS-staged f32 / bias / residual rows
-int launch8_h16(const P& p, int batch, hipStream_t st) {
-  if (p.split_k > 1 || p.act == 4 || p.act == 5 || p.act == 6) return CT_EINVAL;
-  // the VQ distance GEMM on fp16 operands (round 6): the argmax epilogue works on the f32 sums
-  if (p.act == 3) return p.x3 ? CT_EINVAL : launch8<true, true, 3, true>(p, batch, st);
-  if (p.x3) {
-    // split-fp16 operands: the GEGLU pair epilogue, f32 rows (bias / f32 residual / bf16 copy)
-    if (p.act == 2) return launch8<true, true, 2, true, true>(p, batch, st);
-    if (!p.c_f32 || p.act != 0) return CT_EINVAL;
-    if (p.R && p.r_f32 && !p.accumulate) return launch8<true, true, -2, true, true>(p, batch, st);
-    if (p.R) return CT_EINVAL;
-    return launch8<true, true, -1, true, true>(p, batch, st);
-  }
-  const bool tr = !p.c_f32 && !p.R;
-  if (p.act == 2) return launch8<true, true, 2, true>(p, batch, st);
-  if (tr) return launch8<true, true, 0, true>(p, batch, st);
-  if (p.R && p.r_f32 && p.c_f32 && p.act == 0 && !p.accumulate) return launch8<true, true, -2, true>(p, batch, st);
-  return launch8<true, true, -1, true>(p, batch, st);
+// Every gemm8p_kernel the library holds: X(EP, H16, X3, layouts it is built for).  launch_plan()
+// below is the only place that names an instantiation; a plan without a row is CT_EINVAL.
+#define ANY_LAYOUT(ak, bk) true
+#define A_KCONTIG(ak, bk) (ak)
+#define AB_KCONTIG(ak, bk) ((ak) && (bk))
+#define GEMM8P_KERNELS(X)                                                                                        \
+  /* bf16 */                                                                                                     \
+  X(EP_ROWS, false, false, ANY_LAYOUT) X(EP_ROWS_RES, false, false, ANY_LAYOUT)                                  \
+  X(EP_ARGMAX_ROWS, false, false, ANY_LAYOUT) X(EP_SLABS, false, false, ANY_LAYOUT)                              \
+  X(EP_TR, false, false, ANY_LAYOUT) X(EP_TR_GEGLU, false, false, ANY_LAYOUT)                                    \
+  X(EP_TR_ARGMAX, false, false, ANY_LAYOUT) X(EP_TR_L2N, false, false, ANY_LAYOUT)                               \
+  X(EP_TR_RELAY, false, false, ANY_LAYOUT) X(EP_TR_GEGLU_RELAY, false, false, ANY_LAYOUT)                        \
+  X(EP_GEGLU_BWD_ROWS, false, false, ANY_LAYOUT) X(EP_TR_QKV_LNFOLD, false, false, AB_KCONTIG)                   \
+  X(EP_LN_FWD, false, false, A_KCONTIG) X(EP_LN_BWD, false, false, A_KCONTIG) X(EP_LNFOLD_BWD, false, false, A_KCONTIG) \
+  /* fp16 */                                                                                                     \
+  X(EP_ROWS, true, false, AB_KCONTIG) X(EP_ROWS_RES, true, false, AB_KCONTIG) X(EP_TR, true, false, AB_KCONTIG)  \
+  X(EP_TR_GEGLU, true, false, AB_KCONTIG) X(EP_TR_ARGMAX, true, false, AB_KCONTIG)                               \
+  X(EP_LN_FWD, true, false, AB_KCONTIG) X(EP_TR_QKV_LNFOLD, true, false, AB_KCONTIG)                             \
+  /* split-fp16 (x3) */                                                                                          \
+  X(EP_ROWS, true, true, AB_KCONTIG) X(EP_ROWS_RES, true, true, AB_KCONTIG) X(EP_TR_GEGLU, true, true, AB_KCONTIG)
+
+template <bool AK, bool BKC>
+int launch_plan(const Plan& pl, const P& p, hipStream_t st) {
+  if (!pl.eight) return launch_old<AK, BKC>(p, pl.grid, st);
+#define X(EP, H16, X3, LAYOUTS)                                 \
+  if constexpr (LAYOUTS(AK, BKC))                               \
+    if (pl.ep == EP && pl.h16 == H16 && pl.x3 == X3) return launch8<AK, BKC, EP, H16, X3>(p, pl.grid, st);
+  GEMM8P_KERNELS(X)
+#undef X
+  return CT_EINVAL;
 }
 
-template <bool AK>
-int launch8_any(const P& p, bool bk, int batch, hipStream_t st) {
-  return bk ? launch8_ep<AK, true>(p, batch, st) : launch8_ep<AK, false>(p, batch, st);
+// plan, finish the parameter block from it, launch
+static int run(P& p, bool ak, bool bk, bool h16, int ep_fixed, void* stream) {
+  const Plan pl = make_plan(p, ak, bk, h16, ep_fixed);
+  if (pl.rc) return pl.rc;
+  p.kper = pl.kper;
+  p.stagger = pl.stagger;
+  p.pre1 = pl.pre1;
+  return by_layout(ak, bk, [&](auto AK, auto BKC) {
+    return launch_plan<decltype(AK)::value, decltype(BKC)::value>(pl, p, (hipStream_t)stream);
+  });
 }
 
-}  // namespace g256
-
-// called from ctclip_gemm (gemm.hip) after argument validation
-int ctclip_gemm256(const ctclip_gemm_args* a, int split, int batch, void* stream) {
-  using namespace g256;
-  P p{};
+// the parameter-block fields every entry point sets the same way; the rest start as zero
+static P fill(const ctclip_gemm_args* a, int split, int batch) {
+  P p;
   memset(&p, 0, sizeof(p));
   p.M = a->M; p.N = a->N; p.K = a->K;
   p.A = (const u16*)a->A; p.lda = a->lda;
   p.B = (const u16*)a->B; p.ldb = a->ldb;
-  p.C = a->C; p.ldc = a->ldc; p.c_f32 = a->c_f32;
+  p.C = a->C; p.ldc = a->ldc;
   p.C2 = (u16*)a->C2; p.ldc2 = a->ldc2;
+  p.alpha = a->alpha;
+  p.split_k = split;
+  p.gz = batch * split;
+  return p;
+}
+
+}  // namespace g256
+
+// called from ctclip_gemm (gemm.hip) after argument validation, for the shapes its routes_to_256()
+// names and for x3 operands
+int ctclip_gemm256(const ctclip_gemm_args* a, int split, int batch, void* stream) {
+  using namespace g256;
+  P p = fill(a, split, batch);
+  p.c_f32 = a->c_f32;
   p.bias = a->bias;
   p.R = a->R; p.ldr = a->ldr; p.r_f32 = a->r_f32;
-  p.alpha = a->alpha; p.act = a->act; p.accumulate = a->accumulate; p.split_k = split;
+  p.act = a->act; p.accumulate = a->accumulate;
   p.sA = a->sA; p.sB = a->sB; p.sC = a->sC; p.sC2 = a->sC2; p.sR = a->sR;
   p.n2 = a->n2;
-  p.fold_cs = nullptr;
-  p.nfold = 0;
   p.h16 = a->ab_f16 || a->r_f16;
-  p.ln_y16 = nullptr;
   p.x3 = a->A_lo != nullptr;
-  p.alo = (const u16*)a->A_lo;
-  p.blo = (const u16*)a->B_lo;
+  p.alo = (const u16*)a->A_lo; p.blo = (const u16*)a->B_lo;
   p.C3 = (u16*)a->C3; p.ldc3 = a->ldc3;
   p.C4 = (u16*)a->C4; p.ldc4 = a->ldc4;
-  const int kstep = (variant() == 8 || a->act == 4 || a->act == 5) ? p8::BKK : BK;
-  p.kper = (a->K / kstep + split - 1) / split * kstep;
-  p.gz = batch * split;
   p.persist = g_persist;
   p.epi_lds = g_epi_lds;
   p.group_gx = 8;   // r02: FF1 (11 tiles) -2%, VQ (32) -17%; N <= 6 tiles: neutral to +4% (not grouped)
   p.group_gm = 8;
-  // 8-phase default: stagger only the GEGLU GEMM, whose epilogue (h + g stores + erf) is long
-  // enough that desynchronised CUs pay off (r01 sweep: 0.52 -> 0.48 ms at B = 8; neutral to
-  // slightly negative on the plain / residual epilogues)
-  // (round 4 sweep, profiles/r04a_stagger.log, interleaved rounds: no start stagger is best for the
-  // GEGLU GEMM now -- 0.4229 vs 0.4289 ms at the old default 4; the GEGLU backward gains ~1.5 % at 8)
-  p.stagger = variant() == 8 ? (g_stagger8 >= 0 ? g_stagger8 : (a->act == 4 ? 8 : 0)) : 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (a->ab_f16) {
-    if (!a->a_kcontig || !a->b_kcontig) return CT_EINVAL;
-    p.stagger = 0;
-    return launch8_h16(p, batch, st);
-  }
-  if (variant() == 8 || a->act == 4 || a->act == 5)
-    return a->a_kcontig ? launch8_any<true>(p, a->b_kcontig, batch, st) : launch8_any<false>(p, a->b_kcontig, batch, st);
-  if (tile_rows() == 2) return launch_any<2>(p, a->a_kcontig, a->b_kcontig, batch, st);
-  return launch_any<1>(p, a->a_kcontig, a->b_kcontig, batch, st);
+  return run(p, a->a_kcontig, a->b_kcontig, a->ab_f16, EP_BY_ARGS, stream);
 }
 
 // LayerNorm-fused N = 512 GEMM (include/ctclip_hip.h).  The pair exchange needs the persistent
@@ -1834,8 +1861,8 @@ extern "C" int ctclip_gemm_ln(const ctclip_gemm_args* a, const ctclip_ln_epilogu
   if (!a || !ln || (ln->mode != 1 && ln->mode != 2)) return CT_EINVAL;
   if (a->M == 0) return 0;
   CT_REQUIRE(a->N == 512 && a->M > 0 && a->M % 2048 == 0 && a->K > 0 && a->K % 64 == 0, CT_ESHAPE);
-  CT_REQUIRE(a->split_k <= 1 && a->batch <= 1 && a->act == 0 && !a->accumulate && a->c_f32 && !a->B2, CT_EINVAL);
-  CT_REQUIRE(variant() == 8 && g_persist != 0 && g_grid_cap == 0, CT_EINVAL);
+  CT_REQUIRE(a->split_k <= 1 && a->batch <= 1 && a->act == ACT_NONE && !a->accumulate && a->c_f32 && !a->B2, CT_EINVAL);
+  CT_REQUIRE(g_variant == 8 && g_persist != 0 && g_grid_cap == 0, CT_EINVAL);
   CT_REQUIRE(aligned16(a->A) && aligned16(a->B) && aligned16(a->C) && a->lda % 8 == 0 && a->ldb % 8 == 0 &&
                  a->ldc % 8 == 0, CT_EALIGN);
   if (a->C2) CT_REQUIRE(aligned16(a->C2) && a->ldc2 % 8 == 0, CT_EALIGN);
@@ -1855,22 +1882,12 @@ extern "C" int ctclip_gemm_ln(const ctclip_gemm_args* a, const ctclip_ln_epilogu
     CT_REQUIRE(ln->X && aligned16(ln->X) && ln->ldx % 8 == 0 && ln->part_gamma && !ln->beta && a->C2 && a->R,
                CT_EINVAL);
   }
-  P p{};
-  memset(&p, 0, sizeof(p));
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.A = (const u16*)a->A; p.lda = a->lda;
-  p.B = (const u16*)a->B; p.ldb = a->ldb;
-  p.C = a->C; p.ldc = a->ldc; p.c_f32 = 1;
-  p.C2 = (u16*)a->C2; p.ldc2 = a->ldc2;
+  P p = fill(a, 1, 1);
+  p.c_f32 = 1;
   p.bias = a->bias;
   p.R = a->R; p.ldr = a->ldr; p.r_f32 = 1;
-  p.alpha = a->alpha; p.act = 0; p.accumulate = 0; p.split_k = 1;
-  p.kper = a->K;
-  p.debug = 0;
   p.group_gx = 1 << 30;   // plain row-major tile order: the pairing above relies on it
-  p.stagger = 0;
-  p.gz = 1;
-  p.persist = 1;
+  p.persist = 1;          // whatever ctclip_gemm_set_persist says (refused above when it says 0)
   p.ln_gamma = ln->gamma; p.ln_beta = ln->beta; p.ln_eps = ln->eps;
   p.ln_y = (u16*)ln->Y; p.ln_ldy = ln->ldy;
   p.ln_mean = ln->mean; p.ln_rstd = ln->rstd;
@@ -1882,14 +1899,9 @@ extern "C" int ctclip_gemm_ln(const ctclip_gemm_args* a, const ctclip_ln_epilogu
   p.spin_limit = ln->spin_limit ? ln->spin_limit : LN_SPIN_LIMIT;
   p.ln_debug = ln->debug;
   p.ln_y16 = ln->mode == 1 ? (u16*)ln->Y16 : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!a->a_kcontig) return CT_EINVAL;
-  if (a->ab_f16) {   // fp16 operands: the forward form only, B K-contiguous
-    if (ln->mode != 1 || !a->b_kcontig) return CT_EINVAL;
-    return launch8<true, true, -6, true>(p, 1, st);
-  }
-  if (ln->mode == 1) return a->b_kcontig ? launch8<true, true, -6>(p, 1, st) : launch8<true, false, -6>(p, 1, st);
-  return a->b_kcontig ? launch8<true, true, -7>(p, 1, st) : launch8<true, false, -7>(p, 1, st);
+  // A K-contiguous; fp16 operands in the forward form with B K-contiguous only: launch_plan has no
+  // other kernel and answers CT_EINVAL
+  return run(p, a->a_kcontig, a->b_kcontig, a->ab_f16, ln->mode == 1 ? EP_LN_FWD : EP_LN_BWD, stream);
 }
 
 // Q | K | V projection of one transformer layer as ONE GEMM over the raw residual rows, with the
@@ -1911,25 +1923,17 @@ extern "C" int ctclip_gemm_qkv_lnfold2(const ctclip_gemm_args* a, const float* m
   CT_REQUIRE(a->M > 0 && a->N % 256 == 0 && a->K > 0 && a->K % 64 == 0, CT_ESHAPE);
   CT_REQUIRE(nfold > 0 && nfold % 256 == 0 && nfold < a->N && a->n2 > nfold && a->n2 % 64 == 0 && a->n2 <= a->N,
              CT_EINVAL);
-  CT_REQUIRE(a->a_kcontig && a->b_kcontig && !a->c_f32 && a->C2 && a->bias && !a->R && !a->B2 && a->act == 5 &&
+  CT_REQUIRE(a->a_kcontig && a->b_kcontig && !a->c_f32 && a->C2 && a->bias && !a->R && !a->B2 && a->act == ACT_L2N &&
                  a->split_k <= 1 && a->batch <= 1 && !a->accumulate,
              CT_EINVAL);
-  CT_REQUIRE(variant() == 8, CT_EINVAL);
+  CT_REQUIRE(g_variant == 8, CT_EINVAL);
   CT_REQUIRE(aligned16(a->A) && aligned16(a->B) && aligned16(a->C) && aligned16(a->C2) && aligned16(a->bias) &&
                  aligned16(fold_cs) && a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 8 == 0 && a->ldc2 % 8 == 0,
              CT_EALIGN);
-  P p{};
-  memset(&p, 0, sizeof(p));
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.A = (const u16*)a->A; p.lda = a->lda;
-  p.B = (const u16*)a->B; p.ldb = a->ldb;
-  p.C = a->C; p.ldc = a->ldc; p.c_f32 = 0;
-  p.C2 = (u16*)a->C2; p.ldc2 = a->ldc2;
+  P p = fill(a, 1, 1);
   p.bias = a->bias;
-  p.alpha = a->alpha; p.act = 5; p.split_k = 1;
+  p.act = ACT_L2N;
   p.n2 = a->n2;
-  p.kper = a->K;
-  p.gz = 1;
   p.persist = g_persist;
   p.group_gx = 8;
   p.ln_mean = (float*)mean;
@@ -1937,8 +1941,7 @@ extern "C" int ctclip_gemm_qkv_lnfold2(const ctclip_gemm_args* a, const float* m
   p.fold_cs = fold_cs;
   p.nfold = nfold;
   p.c_col0 = c_col0;
-  if (a->ab_f16) return launch8<true, true, 8, true>(p, 1, (hipStream_t)stream);
-  return launch8<true, true, 8>(p, 1, (hipStream_t)stream);
+  return run(p, true, true, a->ab_f16, EP_TR_QKV_LNFOLD, stream);
 }
 
 // Backward of the folded LayerNorm + Q | K | V projections (include/ctclip_hip.h): with A = [dq o rstd |
@@ -1952,33 +1955,25 @@ extern "C" int ctclip_gemm_lnfold_bwd(const ctclip_gemm_args* a, const void* X, 
   if (!a || !X || !c1 || !beta) return CT_EINVAL;
   if (a->M == 0) return 0;
   CT_REQUIRE(a->M > 0 && a->N > 0 && a->N % 8 == 0 && a->K > 0 && a->K % 64 == 0, CT_ESHAPE);
-  CT_REQUIRE(a->a_kcontig && a->c_f32 && a->R && a->r_f32 && !a->bias && !a->B2 && a->act == 0 && a->split_k <= 1 &&
+  CT_REQUIRE(a->a_kcontig && a->c_f32 && a->R && a->r_f32 && !a->bias && !a->B2 && a->act == ACT_NONE && a->split_k <= 1 &&
                  a->batch <= 1 && !a->accumulate,
              CT_EINVAL);
-  CT_REQUIRE(variant() == 8, CT_EINVAL);
+  CT_REQUIRE(g_variant == 8, CT_EINVAL);
   CT_REQUIRE(aligned16(a->A) && aligned16(a->B) && aligned16(a->C) && aligned16(a->R) && aligned16(X) &&
                  a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 8 == 0 && a->ldr % 8 == 0 && ldx % 8 == 0,
              CT_EALIGN);
   if (a->C2) CT_REQUIRE(aligned16(a->C2) && a->ldc2 % 8 == 0, CT_EALIGN);
-  P p{};
-  memset(&p, 0, sizeof(p));
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.A = (const u16*)a->A; p.lda = a->lda;
-  p.B = (const u16*)a->B; p.ldb = a->ldb;
-  p.C = a->C; p.ldc = a->ldc; p.c_f32 = 1;
-  p.C2 = (u16*)a->C2; p.ldc2 = a->ldc2;
+  P p = fill(a, 1, 1);
+  p.c_f32 = 1;
   p.R = a->R; p.ldr = a->ldr; p.r_f32 = 1;
-  p.alpha = a->alpha; p.split_k = 1;
-  p.kper = a->K;
-  p.gz = 1;
   p.persist = g_persist;
   p.group_gx = 8;
+  // X, c1 and beta travel in the LayerNorm epilogues' fields
   p.ln_x = (const u16*)X;
   p.ln_ldx = ldx;
   p.ln_mean = (float*)c1;
   p.ln_rstd = (float*)beta;
-  hipStream_t st = (hipStream_t)stream;
-  return a->b_kcontig ? launch8<true, true, -8>(p, 1, st) : launch8<true, false, -8>(p, 1, st);
+  return run(p, true, a->b_kcontig, false, EP_LNFOLD_BWD, stream);   // bf16 operands only
 }
 
 // A/B switch: the transposed bf16 / GEGLU epilogues' stores through the wave's LDS scratch
@@ -2011,9 +2006,10 @@ extern "C" int ctclip_gemm_set_persist(int v) {
   return old;
 }
 
-// diagnostic: select the large-tile kernel variant at run time (returns the previous one)
+// diagnostic: select the large-tile kernel at run time, 8 (8-phase) or 1 (old); any other value
+// changes nothing.  Returns the previous one.
 extern "C" int ctclip_gemm_set_variant(int v) {
-  const int old = g256::variant();
-  if (v == 1 || v == 2 || v == 8) g256::g_variant = v;
+  const int old = g256::g_variant;
+  if (v == 1 || v == 8) g256::g_variant = v;
   return old;
 }

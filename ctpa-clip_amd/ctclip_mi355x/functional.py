@@ -307,7 +307,7 @@ def _adjacent(ts, arena_of):
 # activations and weights.  SURVEY 8(c): compared to the build's own bf16 path, tolerance per test.
 _FP8 = {'on': False}
 # The attention's pre-norm LayerNorm folded into ONE Q | K | V projection over the PEG output
-# (gemm256.hip EP 8, ctclip_gemm_qkv_lnfold): PEG leaves the LayerNorm statistics, the Q columns
+# (gemm256.hip EP_TR_QKV_LNFOLD, ctclip_gemm_qkv_lnfold): PEG leaves the LayerNorm statistics, the Q columns
 # compute LN(x) Wq^T = rstd (x (gamma o Wq)^T - mean Wq gamma), so neither the LayerNorm kernel
 # nor its output exists; the Q weight gradient uses the same fold (ctclip_lnfold_wgrad).
 # CTCLIP_LN1_FOLD=0: the LayerNorm kernel and the two projections (A/B switch).
@@ -648,7 +648,7 @@ class ViTLayerFn(torch.autograd.Function):
                          want_o16=f16, eval_only=lean)
         o, lse = att[0], att[1]
         o_in, Wo_in = (att[2], h16(Wo)) if f16 else (o, Wo_b)   # to_out's operands
-        # to_out + residual + the FeedForward's LayerNorm in one launch (gemm256.hip, EP -6) -- only
+        # to_out + residual + the FeedForward's LayerNorm in one launch (gemm256.hip, EP_LN_FWD) -- only
         # where a caller checks the launch's status word every step (kernels.ln_guard: the trainer)
         fused = None if fp8 or not K.ln_guarded() else K.linear_residual_ln(o_in, Wo_in, x1f, ff_w, ff_b, 1e-5,
                                                                             y16=f16, eval_only=lean)
@@ -722,7 +722,7 @@ class ViTLayerFn(torch.autograd.Function):
         if gsink(W2) is not None:
             K.matmul_tn(dx3b, g, tag='dw', flops=2.0 * M_ * W2.shape[0] * W2.shape[1],
                         unpack=(gsink(W2), None, W2.shape[1]))
-        # dx2 = LN'(dh . W1) + dx3 in one launch where the shape allows (gemm256.hip, EP -7)
+        # dx2 = LN'(dh . W1) + dx3 in one launch where the shape allows (gemm256.hip, EP_LN_BWD)
         fused = K.matmul_nn_ln_bwd(dh_, W1p, x2b, m2, r2, ff_w, dx3f, dgamma_out=gsink(ff_w),
                                    dbeta_out=gsink(ff_b)) if K.ln_guarded() else None
         if fused is None:
@@ -789,7 +789,7 @@ class ViTLayerFn(torch.autograd.Function):
             K.matmul_tn(dq, xn, out=gsink(Wq), accumulate=True, tag='dw')
             K.matmul_tn(dkv, x1b, out=gsink(Wkv), accumulate=True, tag='dw')
             dx1kv = K.matmul_nn(dkv, Wkv_b, residual=dx2f, out_dtype=F32)
-            # dx1 = LN'(dq . Wq) + (dkv . Wkv + dx2) in one launch where the shape allows (EP -7)
+            # dx1 = LN'(dq . Wq) + (dkv . Wkv + dx2) in one launch where the shape allows (EP_LN_BWD)
             fused = K.matmul_nn_ln_bwd(dq, Wq_b, x1b, m1, r1, norm_g, dx1kv, dgamma_out=gsink(norm_g)) \
                 if fusable else None
             if fused is not None:

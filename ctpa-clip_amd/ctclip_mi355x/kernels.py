@@ -2,6 +2,7 @@
 torch's current HIP stream and returns torch tensors allocated by the caching allocator."""
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -59,15 +60,44 @@ class KernelTimer:
 TIMER = KernelTimer()
 
 
-def gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, C2=None, ldc2=0, bias=None,
-             R=None, ldr=0, alpha=1.0, act=ACT_NONE, accumulate=False, split_k=1, batch=1,
-             sA=0, sB=0, sC=0, sC2=0, sR=0, tag=None, flops=None, n2=0, B2=None, drop=None):
-    end = TIMER(tag, flops if flops is not None else 2.0 * M * N * K * batch) if tag else None
-    _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, C2=C2, ldc2=ldc2, bias=bias, R=R, ldr=ldr,
-              alpha=alpha, act=act, accumulate=accumulate, split_k=split_k, batch=batch, sA=sA, sB=sB, sC=sC,
-              sC2=sC2, sR=sR, n2=n2, B2=B2, drop=drop)
+@contextlib.contextmanager
+def _timed(tag, flops):
+    """TIMER's event bracket around one tagged launch (nothing without a tag)."""
+    end = TIMER(tag, flops) if tag else None
+    yield
     if end is not None:
         end.record()
+
+
+def _gemm_args(M, N, K, A, B, C, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, ldc=None, C2=None, ldc2=None,
+               bias=None, R=None, ldr=None, alpha=1.0, act=ACT_NONE, accumulate=False, split_k=1, batch=1,
+               sA=0, sB=0, sC=0, sC2=0, sR=0, n2=0, B2=None):
+    """One ctclip_gemm_args.  A leading dimension not given is the tensor's row stride (0 without the
+    tensor); the format flags c_f32, r_f32, r_f16 and ab_f16 follow from the tensors' dtypes."""
+    def ld(t, given):
+        return given if given is not None else t.stride(0) if t is not None else 0
+
+    a = GemmArgs()
+    a.M, a.N, a.K = M, N, K
+    a.A, a.lda, a.a_kcontig = ptr(A), ld(A, lda), int(a_kcontig)
+    a.B, a.ldb, a.b_kcontig = ptr(B), ld(B, ldb), int(b_kcontig)
+    a.C, a.ldc, a.c_f32 = ptr(C), ld(C, ldc), int(C is not None and C.dtype == F32)
+    a.C2, a.ldc2 = ptr(C2), ld(C2, ldc2)
+    a.bias = ptr(bias)
+    a.R, a.ldr, a.r_f32 = ptr(R), ld(R, ldr), int(R is not None and R.dtype == F32)
+    a.alpha, a.act, a.accumulate, a.split_k, a.batch = alpha, act, int(accumulate), split_k, batch
+    a.sA, a.sB, a.sC, a.sC2, a.sR = sA, sB, sC, sC2, sR
+    a.n2 = n2
+    a.B2 = ptr(B2)
+    a.ab_f16 = int(A is not None and A.dtype == F16)
+    a.r_f16 = int(R is not None and R.dtype == F16)
+    return a
+
+
+def gemm_raw(M, N, K, *args, tag=None, flops=None, **kw):
+    """_gemm_raw inside TIMER's bracket for ``tag`` (flops: 2 M N K batch unless given)."""
+    with _timed(tag, flops if flops is not None else 2.0 * M * N * K * kw.get('batch', 1)):
+        _gemm_raw(M, N, K, *args, **kw)
 
 
 def _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, C2=None, ldc2=0, bias=None,
@@ -79,6 +109,7 @@ def _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, C2=None,
     h16 = A.dtype == F16       # fp16 operands (the 3D-ViT forward GEMMs): both, no split-K
     assert B.dtype == A.dtype, (A.dtype, B.dtype)
     s = 1 if h16 else _auto_split(M, N, K, act, split_k, batch, accumulate, C)
+    epilogue = dict(ldc=ldc, C2=C2, ldc2=ldc2, bias=bias, R=R, ldr=ldr)
     if drop is not None:
         assert act == ACT_NONE and not accumulate and C.dtype == F32 and batch == 1 and ldc == N
         if s <= 1:     # no split-K combine to fold it into: GEMM (+ bias), then the dropout kernel
@@ -88,11 +119,7 @@ def _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, C2=None,
             return
         slabs = torch.empty(s, M, N, device=C.device, dtype=F32)
         _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, slabs, N, alpha=alpha, split_k=s, B2=B2)
-        a = GemmArgs()
-        a.C, a.ldc, a.c_f32 = ptr(C), ldc, 1
-        a.C2, a.ldc2 = ptr(C2), ldc2
-        a.bias = ptr(bias)
-        a.R, a.ldr, a.r_f32 = ptr(R), ldr, int(R is not None and R.dtype == F32)
+        a = _gemm_args(M, N, K, None, None, C, **epilogue)
         call('ctclip_reduce_slabs_ep_drop', ptr(slabs), s, M, N, N, _lib.ctypes.byref(a), float(drop[0]),
              int(drop[1]) & (2 ** 64 - 1), stream_ptr())
         return
@@ -101,28 +128,12 @@ def _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, C2=None,
         # workgroups than output tiles, then combine with the epilogue in one pass
         slabs = torch.empty(s, M, N, device=C.device, dtype=F32)
         _gemm_raw(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, slabs, N, alpha=alpha, split_k=s, B2=B2)
-        a = GemmArgs()
-        a.C, a.ldc, a.c_f32 = ptr(C), ldc, int(C.dtype == F32)
-        a.C2, a.ldc2 = ptr(C2), ldc2
-        a.bias = ptr(bias)
-        a.R, a.ldr, a.r_f32 = ptr(R), ldr, int(R is not None and R.dtype == F32)
-        a.act, a.accumulate = act, int(accumulate)
+        a = _gemm_args(M, N, K, None, None, C, act=act, accumulate=accumulate, **epilogue)
         call('ctclip_reduce_slabs_ep', ptr(slabs), s, M, N, N, _lib.ctypes.byref(a), stream_ptr())
         return
-    a = GemmArgs()
-    a.M, a.N, a.K = M, N, K
-    a.A, a.lda, a.a_kcontig = ptr(A), lda, int(a_kcontig)
-    a.B, a.ldb, a.b_kcontig = ptr(B), ldb, int(b_kcontig)
-    a.C, a.ldc, a.c_f32 = ptr(C), ldc, int(C.dtype == F32)
-    a.C2, a.ldc2 = ptr(C2), ldc2
-    a.bias = ptr(bias)
-    a.R, a.ldr, a.r_f32 = ptr(R), ldr, int(R is not None and R.dtype == F32)
-    a.alpha, a.act, a.accumulate, a.split_k, a.batch = alpha, act, int(accumulate), split_k, batch
-    a.sA, a.sB, a.sC, a.sC2, a.sR = sA, sB, sC, sC2, sR
-    a.n2 = n2
-    a.B2 = ptr(B2)
-    a.ab_f16 = int(h16)
-    a.r_f16 = int(R is not None and R.dtype == F16)
+    a = _gemm_args(M, N, K, A, B, C, a_kcontig=a_kcontig, b_kcontig=b_kcontig, lda=lda, ldb=ldb, alpha=alpha, act=act,
+                   accumulate=accumulate, split_k=split_k, batch=batch, sA=sA, sB=sB, sC=sC, sC2=sC2, sR=sR, n2=n2,
+                   B2=B2, **epilogue)
     call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
 
 
@@ -148,17 +159,9 @@ def linear(x, w, *, bias=None, residual=None, out=None, out_dtype=BF16, act=ACT_
     assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
     if discard_out:
         assert act == ACT_GEGLU and x.dtype == F16 and out2 is not None and out is None
-        a = GemmArgs()
-        a.M, a.N, a.K = M, N, K
-        a.A, a.lda, a.a_kcontig = ptr(x), x.stride(0), 1
-        a.B, a.ldb, a.b_kcontig = ptr(w), w.stride(0), 1
-        a.C, a.ldc = None, N
-        a.C2, a.ldc2 = ptr(out2), out2.stride(0)
-        a.alpha, a.act, a.split_k, a.batch, a.ab_f16 = alpha, ACT_GEGLU, 1, 1, 1
-        end = TIMER(tag, flops if flops is not None else 2.0 * M * N * K) if tag else None
-        call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
-        if end is not None:
-            end.record()
+        a = _gemm_args(M, N, K, x, w, None, ldc=N, C2=out2, alpha=alpha, act=ACT_GEGLU)
+        with _timed(tag, flops if flops is not None else 2.0 * M * N * K):
+            call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
         return None
     if out is None:
         out = torch.empty(M, N, device=x.device, dtype=out_dtype)
@@ -284,27 +287,18 @@ def ln_fusable(M, N, bwd=False):
 def _gemm_ln(M, K, A, B, b_kcontig, C, C2, R, ln, tag=None, flops=None):
     """Returns False (nothing launched) when the library refuses the configuration."""
     assert A.dtype == B.dtype
-    a = GemmArgs()
-    a.ab_f16 = int(A.dtype == F16)
-    a.M, a.N, a.K = M, 512, K
-    a.A, a.lda, a.a_kcontig = ptr(A), A.stride(0), 1
-    a.B, a.ldb, a.b_kcontig = ptr(B), B.stride(0), int(b_kcontig)
-    a.C, a.ldc, a.c_f32 = ptr(C), C.stride(0), 1
-    a.C2, a.ldc2 = ptr(C2), C2.stride(0) if C2 is not None else 0
-    a.R, a.ldr, a.r_f32 = ptr(R), R.stride(0) if R is not None else 0, 1
-    a.alpha, a.act, a.accumulate, a.split_k, a.batch = 1.0, 0, 0, 1, 1
+    assert C.dtype == F32 and (R is None or R.dtype == F32)
+    a = _gemm_args(M, 512, K, A, B, C, b_kcontig=b_kcontig, C2=C2, R=R)
     xb, ep = _xchg(M, A.device)
     ln.xchg, ln.epoch = ptr(xb), ep
     ln.status = ptr(_ln_status(A.device))
     ln.spin_limit, ln.debug = _LN_DEBUG['spin_limit'], _LN_DEBUG['skip_publish']
-    end = TIMER(tag, flops if flops is not None else 2.0 * M * 512 * K) if tag else None
-    rc = _lib.lib().ctclip_gemm_ln(_lib.ctypes.byref(a), _lib.ctypes.byref(ln), stream_ptr())
+    with _timed(tag, flops if flops is not None else 2.0 * M * 512 * K):
+        rc = _lib.lib().ctclip_gemm_ln(_lib.ctypes.byref(a), _lib.ctypes.byref(ln), stream_ptr())
     if rc in (_CT_EINVAL, _CT_ESHAPE):
         return False
     if rc != 0:
         raise _lib.KernelError(f'ctclip_gemm_ln failed: {rc}')
-    if end is not None:
-        end.record()
     return True
 
 
@@ -747,11 +741,9 @@ def patch_ln(video, is_hu, PT, P, offs, eps=1e-5, ld=None, want_f16=False, want_
     out = torch.empty(B * T * Hg * Wg, ld, device=video.device, dtype=BF16) if want_bf16 else None
     out16 = torch.empty(B * T * Hg * Wg, ld, device=video.device, dtype=F16) if want_f16 or want_x3 else None
     out16lo = torch.empty(B * T * Hg * Wg, ld, device=video.device, dtype=F16) if want_x3 else None
-    end = TIMER('patch_ln', 0.0)      # (bench.py: the patch LayerNorm's in-step duration)
-    call('ctclip_patch_ln_x3', ptr(video), int(video.dtype == F32), int(is_hu), B, C, Fr, H, W, PT, P, ptr(offs), eps,
-         ptr(out), ptr(out16), ptr(out16lo), ld, stream_ptr())
-    if end is not None:
-        end.record()
+    with _timed('patch_ln', 0.0):     # (bench.py: the patch LayerNorm's in-step duration)
+        call('ctclip_patch_ln_x3', ptr(video), int(video.dtype == F32), int(is_hu), B, C, Fr, H, W, PT, P, ptr(offs),
+             eps, ptr(out), ptr(out16), ptr(out16lo), ld, stream_ptr())
     if want_x3:
         return out, (out16, out16lo)
     return (out, out16) if want_f16 else out
@@ -894,17 +886,8 @@ def linear_qkv_lnfold(x, wp, cs, mean, rstd, scales, nfold, n2, out=None, out2=N
         out = torch.empty(M, N, device=x.device, dtype=BF16)
     if out2 is None:
         out2 = torch.empty(M, n2, device=x.device, dtype=BF16)
-    a = GemmArgs()
-    a.M, a.N, a.K = M, N, K
-    a.A, a.lda, a.a_kcontig = ptr(x), x.stride(0), 1
-    a.B, a.ldb, a.b_kcontig = ptr(wp), wp.stride(0), 1
-    a.C, a.ldc, a.c_f32 = ptr(out), out.stride(0), 0
-    a.C2, a.ldc2 = ptr(out2), out2.stride(0)
-    a.bias = ptr(scales)
-    a.alpha, a.act, a.split_k, a.batch = 1.0, ACT_L2N, 1, 1
-    a.n2 = n2
-    assert wp.dtype == x.dtype
-    a.ab_f16 = int(x.dtype == F16)     # fp16 x and packed weight (pack_qkv_fold_h16)
+    assert wp.dtype == x.dtype and out.dtype != F32    # fp16 x with the fp16 packed weight (pack_qkv_fold_h16)
+    a = _gemm_args(M, N, K, x, wp, out, C2=out2, bias=scales, act=ACT_L2N, n2=n2)
     call('ctclip_gemm_qkv_lnfold2', _lib.ctypes.byref(a), ptr(mean), ptr(rstd), ptr(cs), nfold, int(c_col0),
          stream_ptr())
     return out, out2
@@ -996,14 +979,8 @@ def matmul_lnfold_bwd(dqkv, wp, res, x, c1, beta, out=None, out2=None):
         out = torch.empty(M, N, device=dqkv.device, dtype=F32)
     if out2 is None:
         out2 = torch.empty(M, N, device=dqkv.device, dtype=BF16)
-    a = GemmArgs()
-    a.M, a.N, a.K = M, N, Kq
-    a.A, a.lda, a.a_kcontig = ptr(dqkv), dqkv.stride(0), 1
-    a.B, a.ldb, a.b_kcontig = ptr(wp), wp.stride(0), 0
-    a.C, a.ldc, a.c_f32 = ptr(out), out.stride(0), 1
-    a.C2, a.ldc2 = ptr(out2), out2.stride(0)
-    a.R, a.ldr, a.r_f32 = ptr(res), res.stride(0), 1
-    a.alpha, a.act, a.split_k, a.batch = 1.0, ACT_NONE, 1, 1
+    assert out.dtype == F32 and res.dtype == F32
+    a = _gemm_args(M, N, Kq, dqkv, wp, out, b_kcontig=False, C2=out2, R=res)
     call('ctclip_gemm_lnfold_bwd', _lib.ctypes.byref(a), ptr(x), x.stride(0), ptr(c1), ptr(beta), stream_ptr())
     return out, out2
 
@@ -1843,20 +1820,15 @@ def pack_rows_x3(src, rows_dst, cols_dst, rowmap=None, colscale=None, scale=X3_W
     return hi, lo
 
 
-def _x3_args(xs, ws, C, alpha):
+def _x3_args(xs, ws, C, alpha, **kw):
     (xh, xl), (wh, wl) = xs, ws
     M, Kd = xh.shape
     N = wh.shape[0]
     assert xh.dtype == F16 and xl.dtype == F16 and wh.dtype == F16 and wl.dtype == F16
     assert xl.shape == xh.shape and xl.stride() == xh.stride() and wl.shape == wh.shape and wl.stride() == wh.stride()
     assert wh.shape[1] == Kd and xh.stride(1) == 1 and wh.stride(1) == 1 and Kd % 64 == 0
-    a = GemmArgs()
-    a.M, a.N, a.K = M, N, Kd
-    a.A, a.lda, a.a_kcontig = ptr(xh), xh.stride(0), 1
-    a.B, a.ldb, a.b_kcontig = ptr(wh), wh.stride(0), 1
+    a = _gemm_args(M, N, Kd, xh, wh, C, alpha=float(alpha), **kw)
     a.A_lo, a.B_lo = ptr(xl), ptr(wl)
-    a.C, a.ldc = ptr(C), C.stride(0)
-    a.alpha, a.split_k, a.batch, a.ab_f16 = float(alpha), 1, 1, 1
     return a
 
 
@@ -1872,17 +1844,11 @@ def linear_x3(xs, ws, *, bias=None, residual=None, want_bf16=False, alpha=1.0 / 
         assert yb.dtype == BF16 and yb.shape == (M, N) and yb.stride(1) == 1
     elif want_bf16:
         yb = torch.empty(M, N, device=y.device, dtype=BF16)
-    a = _x3_args(xs, ws, y, alpha)
-    a.c_f32 = 1
-    a.C2, a.ldc2 = ptr(yb), yb.stride(0) if yb is not None else 0
-    a.bias = ptr(bias)
     if residual is not None:
         assert residual.dtype == F32 and residual.shape == (M, N) and residual.stride(1) == 1
-        a.R, a.ldr, a.r_f32 = ptr(residual), residual.stride(0), 1
-    end = TIMER(tag, flops if flops is not None else 2.0 * M * N * xs[0].shape[1]) if tag else None
-    call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
-    if end is not None:
-        end.record()
+    a = _x3_args(xs, ws, y, alpha, C2=yb, bias=bias, R=residual)
+    with _timed(tag, flops if flops is not None else 2.0 * M * N * xs[0].shape[1]):
+        call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
     return y, yb
 
 
@@ -1896,15 +1862,11 @@ def linear_x3_geglu(xs, w1s, *, alpha=1.0 / X3_WSCALE, want_bf16=True, tag=None,
     gh = torch.empty(M, N // 2, device=dev, dtype=F16)
     gl = torch.empty(M, N // 2, device=dev, dtype=F16)
     gb = torch.empty(M, N // 2, device=dev, dtype=BF16) if want_bf16 else None
-    a = _x3_args(xs, w1s, h, alpha)
-    a.act = ACT_GEGLU
-    a.C2, a.ldc2 = ptr(gh), N // 2
+    a = _x3_args(xs, w1s, h, alpha, act=ACT_GEGLU, C2=gh)
     a.C3, a.ldc3 = ptr(gl), N // 2
     a.C4, a.ldc4 = ptr(gb), N // 2 if gb is not None else 0
-    end = TIMER(tag, flops if flops is not None else 2.0 * M * N * xs[0].shape[1]) if tag else None
-    call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
-    if end is not None:
-        end.record()
+    with _timed(tag, flops if flops is not None else 2.0 * M * N * xs[0].shape[1]):
+        call('ctclip_gemm', _lib.ctypes.byref(a), stream_ptr())
     return h, (gh, gl), gb
 
 

@@ -108,7 +108,7 @@ class StepGuardError(RuntimeError):
 
 
 class LayerNormExchangeError(StepGuardError):
-    """A LayerNorm-fused GEMM (kernels.linear_residual_ln, gemm256.hip EP -6 / -7) gave up waiting for
+    """A LayerNorm-fused GEMM (kernels.linear_residual_ln, gemm256.hip EP_LN_FWD / EP_LN_BWD) gave up waiting for
     its partner tile's row statistics: that step's LayerNorm outputs were wrong.  The step's Adam
     update was not applied (the status word is the Adam kernel's skip guard); later steps are not
     applied either until ``kernels.reset_ln_status()``."""

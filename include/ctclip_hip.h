@@ -108,8 +108,8 @@ typedef struct {
   void* C4; int64_t ldc4;
 } ctclip_gemm_args;
 int ctclip_gemm(const ctclip_gemm_args* a, void* stream);
-/* diagnostic: large-tile kernel variant (8 = 8-phase 256x256x64 default, 1 = 128x256x32,
- * 2 = 256x256x32); returns the previous one.  Every variant computes bit-identical results. */
+/* diagnostic: large-tile kernel variant (8 = 8-phase 256x256x64 default, 1 = 128x256x32; any other
+ * value changes nothing); returns the previous one.  Both compute bit-identical results. */
 int ctclip_gemm_set_variant(int variant);
 /* diagnostic: start stagger of the 8-phase kernel (units of ~2k cycles); returns the previous */
 int ctclip_gemm_set_stagger(int units);

@@ -271,3 +271,100 @@ def test_l2norm_epilogue(K, M, N, n2):
         assert _rel(q, q_ref) < 4e-3
     qn_ref = K.l2norm_scale_fwd(q[:, :n2], n2 // 32, 32, sc)
     assert torch.equal(qn, qn_ref)
+
+
+# (A K-contiguous, B K-contiguous, epilogue): the 8-phase kernels that ctclip_gemm's arguments select
+# (gemm256.hip make_plan) and that no other test launches -- found by joining a kernel trace of the
+# GEMM test files with the library's symbol list.
+_PLAN_CASES = (
+    [(False, False, k) for k in ('rows', 'res', 'bf16', 'geglu', 'argmax', 'l2n', 'geglu_bwd')]
+    + [(False, True, k) for k in ('rows', 'res', 'slabs', 'bf16', 'geglu', 'argmax', 'l2n', 'geglu_bwd')]
+    + [(True, False, k) for k in ('slabs', 'geglu', 'argmax', 'l2n')]
+    + [(True, True, k) for k in ('slabs', 'geglu_bwd', 'argmax_f16')])
+
+
+@pytest.mark.parametrize('ak,bk,kind', _PLAN_CASES)
+def test_plan_kernels_by_layout(K, ak, bk, kind):
+    """One launch per (layout, epilogue) at the smallest shape that routes to the 256 tile
+    (gemm.hip routes_to_256: 16 x 10 = 160 tiles, the last row tile ragged) with three K-steps of 64,
+    so the two-buffer ring wraps; the split-K slabs need K / split >= 512.  Reference: torch float32
+    matmul on the same rounded inputs, relative Frobenius error < 1e-5 (f32 outputs) / 1e-2 (16-bit
+    outputs); the 8-phase and the 128x256x32 kernel agree bit for bit (act 4 / 5 and fp16 operands
+    exist in the 8-phase kernel only, where _variants compares its launch modes)."""
+    torch.manual_seed(11)
+    M, N, Kd = 4000, 2560, 1024 if kind == 'slabs' else 192
+    dt = torch.float16 if kind == 'argmax_f16' else torch.bfloat16
+    A = torch.randn(M, Kd, device='cuda').to(dt)
+    B = (torch.randn(N, Kd, device='cuda') * 0.05).to(dt)
+    Am = A if ak else A.t().contiguous()
+    Bm = B if bk else B.t().contiguous()
+    acc = A.float() @ B.float().t()
+    bias = torch.randn(N, device='cuda')
+    res = torch.randn(M, N, device='cuda')
+    scale = torch.rand(32, device='cuda') + 0.5
+    h = torch.randn(M, 2 * N, device='cuda').bfloat16()
+    n2 = N // 2
+
+    def gemm(C, ldc=None, **kw):
+        K._gemm_raw(M, N, Kd, Am, Am.stride(0), ak, Bm, Bm.stride(0), bk, C, C.stride(-2) if ldc is None else ldc, **kw)
+        return C
+
+    def run():
+        f32 = lambda *s: torch.empty(*s, device='cuda', dtype=torch.float32)  # noqa: E731
+        b16 = lambda *s: torch.empty(*s, device='cuda', dtype=torch.bfloat16)  # noqa: E731
+        if kind == 'rows':
+            return gemm(f32(M, N))
+        if kind == 'res':
+            return gemm(f32(M, N), bias=bias, R=res, ldr=N)
+        if kind == 'slabs':
+            return gemm(f32(2, M, N), split_k=2)
+        if kind == 'bf16':
+            return gemm(b16(M, N))
+        if kind == 'geglu':
+            g = b16(M, N // 2)
+            return torch.cat([gemm(b16(M, N), act=K.ACT_GEGLU, C2=g, ldc2=N // 2), g], 1)
+        if kind in ('argmax', 'argmax_f16'):
+            return gemm(f32(M, N // 64, 2), ldc=N // 64, act=K.ACT_ARGMAX)   # (value, index) pairs
+        if kind == 'l2n':
+            qn = b16(M, n2)
+            return torch.cat([gemm(b16(M, N), act=K.ACT_L2N, C2=qn, ldc2=n2, bias=scale, n2=n2), qn], 1)
+        return gemm(b16(M, 2 * N), act=K.ACT_GEGLU_BWD, R=h, ldr=2 * N)
+    outs = _variants(K, run)
+    out = outs[8]
+    assert torch.equal(out, outs[1])
+    if kind == 'rows':
+        assert _rel(out, acc) < 1e-5
+    elif kind == 'res':
+        assert _rel(out, acc + bias + res) < 1e-5
+    elif kind == 'slabs':
+        assert _rel(out.sum(0), acc) < 1e-5
+    elif kind == 'bf16':
+        assert _rel(out, acc) < 1e-2
+    elif kind == 'geglu':
+        hb = acc.bfloat16().float()
+        hv = hb.view(M, N // 64, 2, 32)
+        g = (torch.nn.functional.gelu(hv[:, :, 1]) * hv[:, :, 0]).reshape(M, N // 2)
+        assert _rel(out[:, :N], hb) < 1e-2
+        assert _rel(out[:, N:], g) < 1e-2
+    elif kind in ('argmax', 'argmax_f16'):
+        groups = acc.view(M, N // 64, 64)
+        best = groups.max(-1).values
+        idx = out[..., 1].contiguous().view(torch.int32).long()
+        col0 = torch.arange(N // 64, device='cuda') * 64
+        assert ((idx >= col0) & (idx < col0 + 64)).all()
+        assert _rel(out[..., 0], best) < 1e-5
+        # the chosen column is the reference's maximum, up to that tolerance
+        assert _rel(groups.gather(-1, (idx - col0).unsqueeze(-1)).squeeze(-1), best) < 1e-5
+    elif kind == 'l2n':
+        heads = acc[:, :n2].view(M, n2 // 32, 32)
+        qn = (torch.nn.functional.normalize(heads, dim=-1) * scale).reshape(M, n2)
+        assert _rel(out[:, :N], acc) < 1e-2
+        assert _rel(out[:, N:], qn) < 1e-2
+    else:
+        hv = h.float().view(M, N // 32, 2, 32)
+        x, gt = hv[:, :, 0], hv[:, :, 1]
+        d = acc.bfloat16().float().view(M, N // 32, 32)
+        cdf = 0.5 * (1 + torch.erf(gt / 2 ** 0.5))
+        pdf = torch.exp(-0.5 * gt * gt) / (2 * torch.pi) ** 0.5
+        ref = torch.stack([d * torch.nn.functional.gelu(gt), d * x * (cdf + gt * pdf)], 2).reshape(M, 2 * N)
+        assert _rel(out, ref) < 1e-2

@@ -1,6 +1,6 @@
 """Weight-gradient (split-K, reduction over the 110,592 tokens) GEMM shapes of the 3D-ViT step on the
-three large-tile kernel variants (ctclip_gemm_set_variant: 8 = 8-phase 256x256x64, one workgroup
-per CU; 1 = 128x256x32, two workgroups per CU; 2 = 256x256x32 4-slot ring), at the split the
+two large-tile kernel variants (ctclip_gemm_set_variant: 8 = 8-phase 256x256x64, one workgroup
+per CU; 1 = 128x256x32, two workgroups per CU), at the split the
 library picks and at 2x / 0.5x that split.  The dW GEMMs are the step's largest kernel family
 (41 launches, ~5.5 ms) and run at ~45 % MFMA busy with HBM at ~2.6 TB/s: latency-bound.
 Interleaved rounds in one process; median ms of the GEMM + slab reduction.
@@ -41,7 +41,7 @@ def main():
               'Q 256x512': (256, 512), 'Wo 512x256': (512, 256)}
     L = _lib.lib()
     confs = []
-    for v in (8, 1, 2):
+    for v in (8, 1):
         for f in (1.0, 2.0, 0.5):
             confs.append((v, f))
     res = {(sh, c): [] for sh in shapes for c in confs}

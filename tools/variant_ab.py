@@ -1,7 +1,6 @@
-"""The forward / dX GEMM shapes of the 3D-ViT step on the three large-tile kernel variants
+"""The forward / dX GEMM shapes of the 3D-ViT step on the two large-tile kernel variants
 (ctclip_gemm_set_variant: 8 = 8-phase 256x256x64 persistent, one workgroup per CU; 1 = 128x256x32,
-two workgroups per CU -- one's epilogue can run beside the other's main loop; 2 = 256x256x32 4-slot
-ring).  The GEGLU backward (act 4) and l2norm (act 5) epilogues exist only in the 8-phase kernel.
+two workgroups per CU -- one's epilogue can run beside the other's main loop).  The GEGLU backward (act 4) and l2norm (act 5) epilogues exist only in the 8-phase kernel.
 Interleaved rounds in one process; median ms.  usage: python tools/variant_ab.py   (GPU)"""
 import os
 import statistics
@@ -43,7 +42,7 @@ def main():
         'dX K=512': lambda: K.matmul_nn(x512, wkv),
     }
     L = _lib.lib()
-    vals = (8, 1, 2)
+    vals = (8, 1)
     res_ms = {(c, v): [] for c in cases for v in vals}
     outs = {}
     for rnd in range(3):
