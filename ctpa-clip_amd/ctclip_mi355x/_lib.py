@@ -178,6 +178,18 @@ class ProbeArgs(ctypes.Structure):
     ]
 
 
+class FilipArgs(ctypes.Structure):
+    """ctclip_filip_args (include/ctclip_hip.h): the fine-grained token-wise contrastive loss."""
+    _fields_ = [
+        ('t_raw', c_vp), ('i_raw', c_vp), ('mask', c_vp), ('log_temp', c_vp),
+        ('Bg', c_i32), ('T', c_i32), ('I', c_i32), ('Dl', c_i32),
+        ('decoupled', c_i32), ('i2t_over_text', c_i32),
+        ('loss', c_vp), ('dt_raw', c_vp), ('di_raw', c_vp), ('dlogtemp', c_vp),
+        ('A', c_vp), ('C', c_vp), ('idx_t2i', c_vp), ('idx_i2t', c_vp),
+        ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 # name -> argtypes (restype is int32 unless _RESTYPES names another)
 _SIGS = {
     'ctclip_version': [],
@@ -313,6 +325,8 @@ _SIGS = {
     'ctclip_mlm_scatter': [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp],
     'ctclip_probe_step': [ctypes.POINTER(ProbeArgs), c_vp],
     'ctclip_probe_step_ws_bytes': [ctypes.POINTER(ProbeArgs)],
+    'ctclip_filip_loss': [ctypes.POINTER(FilipArgs), c_vp],
+    'ctclip_filip_ws_bytes': [ctypes.POINTER(FilipArgs)],
     'ctclip_sgemm': [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
                      c_i32, c_f32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp],
     'ctclip_embed_fwd': [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -324,7 +338,7 @@ _SIGS = {
 }
 _RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_retrieval_ranks_ws_bytes': c_i64,
              'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64,
-             'ctclip_probe_step_ws_bytes': c_i64}
+             'ctclip_probe_step_ws_bytes': c_i64, 'ctclip_filip_ws_bytes': c_i64}
 
 
 def register(name, argtypes):

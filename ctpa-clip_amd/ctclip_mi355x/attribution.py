@@ -28,6 +28,7 @@ import torch
 from . import kernels as K
 from . import precise
 from . import zero_shot as Z
+from .ct_clip import require_cls_latents
 
 WHICH = ('log_odds', 'scores')
 
@@ -57,6 +58,7 @@ class ZeroShotAttribution:
     """``maps(volumes)`` for a ``zero_shot.ZeroShotClassifier`` with its prompts set."""
 
     def __init__(self, classifier):
+        require_cls_latents(classifier.model, 'ZeroShotAttribution')
         self.classifier = classifier
         self._cache = {}        # which -> (key, t_raw the key refers to, [V chunks])
 

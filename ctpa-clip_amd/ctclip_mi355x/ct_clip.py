@@ -11,6 +11,9 @@ encoders: decoupled_contrastive_learning (ct_clip.py:865-867), extra_latent_proj
 one-workgroup kernel as before; any of the three options switches the loss to
 ``functional.ClipLossExFn`` (one workgroup per view pair + a fixed-order reduction).
 Above 128 gathered rows both Functions take the tiled MFMA loss (``functional.set_loss_tiled``).
+``use_all_token_embeds`` (the fine-grained FILIP loss, :751-755,:829-843) takes a branch of its own,
+``_forward_filip`` on ``functional.FilipLossFn`` (csrc/filip.hip): every report token
+against every spatial image token, one view, no extra projection, one rank.
 ``aug_text`` (the reference itself cannot run it: it calls ``.shape`` on a BatchEncoding) and
 everything else raises.
 """
@@ -61,6 +64,14 @@ def l2norm(t):
     return nn.functional.normalize(t, dim=-1)
 
 
+def require_cls_latents(model, who):
+    """The evaluators (zero-shot, retrieval, attribution, linear probe) score ONE latent per report and
+    volume: a ``use_all_token_embeds`` model, whose heads project tokens, is refused by name."""
+    if getattr(model, 'use_all_token_embeds', False):
+        raise NotImplementedError(f'{who} with CTCLIP(use_all_token_embeds=True): the model has no pooled latent '
+                                  'pair (its projections act on tokens)')
+
+
 class CTCLIP(nn.Module):
     def __init__(self, *, image_encoder=None, text_encoder=None, dim_text=512, dim_image=512, dim_latent=512,
                  num_text_tokens=28897, text_enc_depth=6, text_seq_len=256, text_heads=8, text_dim_head=64,
@@ -73,16 +84,30 @@ class CTCLIP(nn.Module):
                  visual_ssl_hidden_layer=-1, simclr_temperature=0.1, image_ssl_loss_weight=0.05,
                  multiview_loss_weight=0.1, checkpoint_during_training=False, **kwargs):
         super().__init__()
-        unsupported = dict(use_all_token_embeds=use_all_token_embeds, downsample_image_embeds=downsample_image_embeds,
+        # use_all_token_embeds projects ONE spatial token of the image tower: the tower has to state its token
+        # width (``.dim``, as CTViT does) and ``dim_image`` has to be that width.  With the flattened width
+        # (h w d, the CLS configuration's) the pooled volume would be taken for a single token without an error
+        token_width = getattr(image_encoder, 'dim', None)
+        no_tokens = bool(use_all_token_embeds) and (token_width is None or int(token_width) != int(dim_image))
+        unsupported = dict(use_all_token_embeds=no_tokens, downsample_image_embeds=downsample_image_embeds,
                            use_mlm=use_mlm,
                            use_visual_ssl=use_visual_ssl or visual_ssl is not None,
                            text_causal_mask=text_causal_mask)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
-            raise NotImplementedError(f'CTCLIP options outside the contrastive hot path: {bad}')
+            hint = (f' (use_all_token_embeds needs an image encoder whose token width ``.dim`` equals dim_image = '
+                    f'{dim_image}, got {token_width}; models.build_ctclip sets it)') if no_tokens else ''
+            raise NotImplementedError(f'CTCLIP options outside the contrastive hot path: {bad}{hint}')
         if image_encoder is None or text_encoder is None:
             raise NotImplementedError('the built-in VisionTransformer / TextTransformer are never used by the '
                                       'reference (pretrained_model.py:31-42); pass image_encoder and text_encoder')
+        if use_all_token_embeds and extra_latent_projection:
+            raise NotImplementedError('CTCLIP: use_all_token_embeds with extra_latent_projection (the fine-grained '
+                                      'loss has one latent pair)')
+        self.use_all_token_embeds = bool(use_all_token_embeds)
+        # use_all_token_embeds: the image -> text denominator over the texts (the FILIP paper) instead of over
+        # the images (the reference, inherited from x-clip); see functional.FilipLossFn
+        self.filip_i2t_over_text = False
         self.dim_text = dim_text
         self.dim_image = dim_image
         self.dim_latent = dim_latent
@@ -290,6 +315,11 @@ class CTCLIP(nn.Module):
         view's contrastive loss is mixed in with ``multiview_loss_weight`` (:882-899)."""
         if aug_text is not None:
             raise NotImplementedError('multiview augmentation is off in the reference configuration')
+        if self.use_all_token_embeds:
+            if aug_image is not None:
+                raise NotImplementedError('CTCLIP: use_all_token_embeds with aug_image (the fine-grained loss has '
+                                          'one image view)')
+            return self._forward_filip(text, image, return_loss, return_encodings, return_latents)
         n_views = 1
         if aug_image is not None:
             aug = tuple(aug_image) if isinstance(aug_image, (tuple, list)) else (aug_image,)
@@ -338,6 +368,51 @@ class CTCLIP(nn.Module):
                                      t_extra.view(1, B, Dl) if extra else None,
                                      i_extra.view(n_views, B, Dl) if extra else None, self.temperature,
                                      bool(self.decoupled_contrastive_learning), 1.0 - w_mv, w_mv, None, tg)
+
+    def _forward_filip(self, text, image, return_loss, return_encodings, return_latents):
+        """``use_all_token_embeds`` (ct_clip.py:751-755, 829-843): every report token against every spatial
+        image token (the pooled volume viewed [B, h*w, d]), both projected token-wise, the fine-grained loss
+        on ``functional.FilipLossFn``.  Plain autograd walks both towers (``defer_text_backward`` is not
+        used); BERT is joined on the current stream.  Without ``return_loss`` the temperature-scaled token
+        similarity [B, T, I] of each pair comes back (the intent of :803), with ``return_latents`` the
+        l2-normalised token latents and the image tokens."""
+        from . import kernels as K
+        if dist_sync.world_rank()[0] > 1:
+            raise NotImplementedError('CTCLIP: use_all_token_embeds under torch.distributed with world size > 1 '
+                                      '(the token latents are not gathered)')
+        vqs = self._vq_state()
+        if vqs is not None:
+            vqs.defer_ema = DEFER_EMA != '0' and self.visual_transformer.training
+        try:
+            pooled, _ = self.visual_transformer.encode_pooled(image)
+        finally:
+            if vqs is not None:
+                vqs.defer_ema = False
+        enc_text = self.text_transformer(text.input_ids, attention_mask=text.attention_mask)[0]
+        if return_encodings:
+            self._flush_ema_in_forward()
+            return enc_text, pooled
+        B, T, dt = enc_text.shape
+        d = self.to_visual_latent.weight.shape[1]
+        tokens = pooled.view(B, -1, d)
+        I, Dl = tokens.shape[1], self.dim_latent
+        t_raw = Fn.TextProjFn.apply(enc_text.reshape(B * T, dt).contiguous(), self.to_text_latent.weight).view(B, T, Dl)
+        i_raw = Fn.TextProjFn.apply(tokens.reshape(B * I, d).contiguous(), self.to_visual_latent.weight).view(B, I, Dl)
+        self._flush_ema_in_forward()
+        if return_latents:
+            return l2norm(t_raw), l2norm(i_raw), tokens
+        if not return_loss:
+            tn, inn = l2norm(t_raw.detach()), l2norm(i_raw.detach())
+            sim = torch.stack([K.smm(tn[b].contiguous(), inn[b].t()) for b in range(B)])
+            return sim * self.temperature.detach().exp()
+        mask = text.attention_mask.to(torch.uint8).contiguous()
+        return Fn.FilipLossFn.apply(t_raw, i_raw, mask, self.temperature, bool(self.decoupled_contrastive_learning),
+                                    bool(self.filip_i2t_over_text))
+
+    def _flush_ema_in_forward(self):
+        # the codebook EMA at encode()'s site: after the projections, unless the trainer owns the step
+        if DEFER_EMA == '1' or (DEFER_EMA in ('2', '3') and not self.ema_after_step):
+            self.flush_ema()
 
     def backward_deferred_text(self):
         """Back-propagate the text tower whose graph ``encode`` detached (defer_text_backward).

@@ -1334,6 +1334,29 @@ class ClipLossExFn(torch.autograd.Function):
         return dt * s, di * s, dtx, dix, (dlt * s * ctx.scale).reshape(()), None, None, None, None, None
 
 
+class FilipLossFn(torch.autograd.Function):
+    """The fine-grained (FILIP) token-wise contrastive loss of ``use_all_token_embeds``
+    (ct_clip/ct_clip.py:829-878) on the fused ``kernels.filip_loss``: ``t_raw`` [B, T, Dl] / ``i_raw``
+    [B, I, Dl] raw token latents, ``mask`` [B, T] the text key mask.  The kernel produces the gradients
+    with the loss; backward only scales them.  One rank only (the token latents are not gathered)."""
+
+    @staticmethod
+    def forward(ctx, t_raw, i_raw, mask, log_temp, decoupled=False, i2t_over_text=False):
+        if dist_sync.world_rank()[0] > 1:
+            raise NotImplementedError('use_all_token_embeds under torch.distributed with world size > 1 '
+                                      '(the token latents are not gathered)')
+        r = K.filip_loss(t_raw.detach(), i_raw.detach(), mask, log_temp.detach().reshape(1).contiguous(),
+                         decoupled=decoupled, i2t_over_text=i2t_over_text)
+        ctx.save_for_backward(r['dt'], r['di'], r['dlt'])
+        return r['loss'].reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dt, di, dlt = ctx.saved_tensors
+        s = dloss.reshape(1)
+        return dt * s, di * s, None, (dlt * s).reshape(()), None, None
+
+
 # ----------------------------------------------------------------------------- BERT
 class BertEmbedFn(torch.autograd.Function):
     """BertEmbeddings: word + position + token_type(0), LayerNorm(eps 1e-12)."""

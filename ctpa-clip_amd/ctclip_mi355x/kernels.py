@@ -1246,6 +1246,46 @@ def clip_loss_tiled(t_raw, i_raw, log_temp, t_extra=None, i_extra=None, decouple
     return loss, dt, di, dtx, dix, dlt, pair
 
 
+def filip_loss(t_raw, i_raw, mask, log_temp, decoupled=False, i2t_over_text=False, want_logits=False,
+               want_idx=False):
+    """The fine-grained (FILIP) token-wise contrastive loss (ctclip_filip_loss, csrc/filip.hip;
+    ct_clip/ct_clip.py:829-878): t_raw [Bg, T, Dl] / i_raw [Bg, I, Dl] raw token latents, mask [Bg, T]
+    uint8 / bool text key mask (every row with a set entry), log_temp [1].  A max attained by several
+    tokens belongs to the lowest index.  ``i2t_over_text``: the image -> text denominator runs over the
+    texts (the FILIP paper) instead of the images (the reference).  Returns a dict: loss [1], dt, di,
+    dlt [1], with ``want_logits`` A, C [Bg, Bg], with ``want_idx`` idx_t2i int32 [Bg, Bg, T] (-1 at
+    masked tokens), idx_i2t int32 [Bg, Bg, I]."""
+    if t_raw.dim() != 3 or i_raw.dim() != 3 or t_raw.shape[0] != i_raw.shape[0] or t_raw.shape[2] != i_raw.shape[2]:
+        raise ValueError(f'filip_loss: t_raw [Bg, T, Dl] / i_raw [Bg, I, Dl], got {tuple(t_raw.shape)} / '
+                         f'{tuple(i_raw.shape)}')
+    if t_raw.dtype != F32 or i_raw.dtype != F32 or log_temp.dtype != F32:
+        raise ValueError('filip_loss: f32 inputs')
+    Bg, T, Dl = t_raw.shape
+    I = i_raw.shape[1]
+    if tuple(mask.shape) != (Bg, T) or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f'filip_loss: mask uint8 / bool {(Bg, T)}, got {mask.dtype} {tuple(mask.shape)}')
+    t_raw, i_raw, mask = t_raw.contiguous(), i_raw.contiguous(), mask.contiguous()
+    dev = t_raw.device
+    res = dict(loss=torch.empty(1, device=dev, dtype=F32), dt=torch.empty_like(t_raw), di=torch.empty_like(i_raw),
+               dlt=torch.empty(1, device=dev, dtype=F32))
+    # A and C always live in tensors of their own (tiny), so the workspace stays within its bound
+    A, C = torch.empty(Bg, Bg, device=dev, dtype=F32), torch.empty(Bg, Bg, device=dev, dtype=F32)
+    if want_logits:
+        res.update(A=A, C=C)
+    if want_idx:
+        res.update(idx_t2i=torch.empty(Bg, Bg, T, device=dev, dtype=torch.int32),
+                   idx_i2t=torch.empty(Bg, Bg, I, device=dev, dtype=torch.int32))
+    a = _lib.FilipArgs(t_raw=ptr(t_raw), i_raw=ptr(i_raw), mask=ptr(mask), log_temp=ptr(log_temp), Bg=Bg, T=T, I=I,
+                       Dl=Dl, decoupled=int(bool(decoupled)), i2t_over_text=int(bool(i2t_over_text)),
+                       loss=ptr(res['loss']), dt_raw=ptr(res['dt']), di_raw=ptr(res['di']), dlogtemp=ptr(res['dlt']),
+                       A=ptr(A), C=ptr(C), idx_t2i=ptr(res.get('idx_t2i')), idx_i2t=ptr(res.get('idx_i2t')))
+    nbytes = _lib.lib().ctclip_filip_ws_bytes(_lib.ctypes.byref(a))
+    ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=F32)
+    a.ws, a.ws_bytes = ptr(ws), nbytes
+    call('ctclip_filip_loss', _lib.ctypes.byref(a), stream_ptr())
+    return res
+
+
 PROBE_OUTPUTS = ('loss', 'dW', 'db', 'Z', 'count')
 
 

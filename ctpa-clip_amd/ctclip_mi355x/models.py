@@ -14,17 +14,21 @@ def build_ctclip(vit=None, bert=None, dim_latent=512, frames=240, **loss_options
     ``bert`` = BertConfig (default: BERT-base as CXR-BERT-specialized).  The flattened image
     embedding width follows from the ViT grid: (image/patch)^2 * dim (ct_clip.py:724,740).
     ``loss_options``: CTCLIP's decoupled_contrastive_learning / extra_latent_projection /
-    multiview_loss_weight (default: the reference configuration, all off / 0.1)."""
+    multiview_loss_weight (default: the reference configuration, all off / 0.1) and
+    use_all_token_embeds (the fine-grained token-wise loss: to_visual_latent then projects one
+    spatial token, so its input width is the ViT token width)."""
     vk = dict(BASE_VIT)
     vk.update(vit or {})
+    loss_options = dict(loss_options)
+    all_tokens = bool(loss_options.pop('use_all_token_embeds', False))
     image_encoder = CTViT(**vk, use_vgg_and_gan=False)
     text_encoder = BertModel(bert or BertConfig())
     grid = vk['image_size'] // vk['patch_size']
-    dim_image = grid * grid * vk['dim']
+    dim_image = vk['dim'] if all_tokens else grid * grid * vk['dim']
     return CTCLIP(image_encoder=image_encoder, text_encoder=text_encoder,
                   dim_text=text_encoder.config.hidden_size, dim_image=dim_image, dim_latent=dim_latent,
                   **{'extra_latent_projection': False, **loss_options}, use_mlm=False,
-                  downsample_image_embeds=False, use_all_token_embeds=False)
+                  downsample_image_embeds=False, use_all_token_embeds=all_tokens)
 
 
 def set_finetune_trainable(model):

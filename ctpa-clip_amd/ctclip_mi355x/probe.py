@@ -19,6 +19,7 @@ from torch import nn
 from . import evaluate as E
 from . import kernels as K
 from . import zero_shot
+from .ct_clip import require_cls_latents
 
 UNLABELLED = 255          # a label entry that is excluded from loss, gradient and count
 
@@ -183,6 +184,7 @@ class LinearProbeEvaluator:
     ``ZeroShotEvaluator.evaluate``'s dict, computed by the same functions of ``evaluate.py``."""
 
     def __init__(self, model, pathologies=zero_shot.PATHOLOGIES, normalize=True):
+        require_cls_latents(model, 'LinearProbeEvaluator')
         self.model = model
         self.pathologies = tuple(pathologies)
         self.normalize = normalize

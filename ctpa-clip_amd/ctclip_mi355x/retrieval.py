@@ -18,6 +18,7 @@ import torch
 
 from . import kernels as K
 from . import zero_shot as Z
+from .ct_clip import require_cls_latents
 from .evaluate import bootstrap_indices, compute_cis
 
 DEFAULT_KS = (1, 5, 10, 50, 100)
@@ -78,6 +79,7 @@ class RetrievalEvaluator:
     """Report <-> volume retrieval metrics of a ``ctclip_mi355x.CTCLIP``."""
 
     def __init__(self, model):
+        require_cls_latents(model, 'RetrievalEvaluator')
         self.model = model
 
     def text_latents(self, text, batch_size=8):

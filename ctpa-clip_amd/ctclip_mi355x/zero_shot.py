@@ -19,6 +19,7 @@ import torch
 
 from . import functional as Fn
 from . import kernels as K
+from .ct_clip import require_cls_latents
 
 # ct_clip/ctclip_inference.py:286-290
 PATHOLOGIES = ('Medical material', 'Arterial wall calcification', 'Cardiomegaly', 'Pericardial effusion',
@@ -54,6 +55,7 @@ class ZeroShotClassifier:
     object with ``.input_ids`` / ``.attention_mask`` of 2P rows) via ``set_prompts``."""
 
     def __init__(self, model, pathologies=PATHOLOGIES, tokenizer=None, max_length=512, template=INFERENCE_TEMPLATE):
+        require_cls_latents(model, 'ZeroShotClassifier')
         self.model = model
         self.pathologies = tuple(pathologies)
         self.max_length = max_length
@@ -123,6 +125,7 @@ class _eval:
 def text_latents(m, text):
     """Raw projected text latents [rows, Dl] of ``text`` (``.input_ids`` / ``.attention_mask``): BERT, the
     CLS row, to_text_latent."""
+    require_cls_latents(m, 'zero_shot.text_latents')
     with torch.no_grad(), _eval(m):
         enc = m.text_transformer(text.input_ids, attention_mask=text.attention_mask)[0]
         return Fn.TextProjFn.apply(enc[:, 0, :].contiguous(), m.to_text_latent.weight)
@@ -130,6 +133,7 @@ def text_latents(m, text):
 
 def image_latents(m, volumes):
     """Raw projected image latents [N, Dl] (image tower + VQ + pool + to_visual_latent)."""
+    require_cls_latents(m, 'zero_shot.image_latents')
     with torch.no_grad(), _eval(m):
         pooled, pooled_b = m.visual_transformer.encode_pooled(volumes)
         W = m.to_visual_latent.weight

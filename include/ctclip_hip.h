@@ -945,6 +945,45 @@ typedef struct {
 int ctclip_probe_step(const ctclip_probe_args* a, void* stream);
 int64_t ctclip_probe_step_ws_bytes(const ctclip_probe_args* a);
 
+/* ---------------------------------------------------------------- fine-grained (FILIP) loss (csrc/filip.hip)
+ * The token-wise contrastive loss of CTCLIP(use_all_token_embeds=True) (ct_clip/ct_clip.py:829-878), one text
+ * and one image view, forward and every gradient from one call.  With tn / in the l2-normalised tokens
+ * (F.normalize rule, eps 1e-12; a zero row gives finite gradients) and temp = exp(log_temp[0]):
+ *   S[x,y,t,i] = temp <tn[x,t], in[y,i]>
+ *   A[x,y] = sum_t mask[x,t] max_i S / max(sum_t mask[x,t], 1e-6)          text -> image
+ *   C[x,y] = (1 / I) sum_i max_{t : mask[x,t]} S                            image -> text
+ *   loss = 1/2 [ mean_x(-log(e^A_xx + 1e-20) + log(sum_y e^A_xy + 1e-20)) + mean_x(the same with C) ]
+ * decoupled: the diagonal is left out of both denominators.  C stays indexed [text, image] and its
+ * denominator runs over the IMAGE index, as the reference (and upstream x-clip) has it; i2t_over_text != 0
+ * sums it over the texts instead (sum_x e^C_xy, the FILIP paper's direction).
+ * TIE RULE: a max attained by several indices belongs to the lowest of them and the whole gradient goes
+ * there (torch.amax splits it), so the backward is a pure function of the stored indices.
+ * S is never written: the products run tile-wise on the f32 matrix pipe (exact f32) and only argmax indices
+ * leave it.  No float atomics, every sum in a fixed order: two runs give the same bits.  Masked text tokens
+ * are never read as scores (64-token tiles of them are skipped) and get zero gradient.
+ * t_raw [Bg][T][Dl], i_raw [Bg][I][Dl] f32 contiguous; mask [Bg][T] bytes (0 = padding), every row with at
+ * least one set entry (a row with none is memory-safe and meaningless).  Outputs: loss [1], dt_raw
+ * [Bg][T][Dl], di_raw [Bg][I][Dl], dlogtemp [1] (= sum_xy dA A + dC C); optional A, C [Bg][Bg], idx_t2i int32
+ * [Bg][Bg][T] (-1 at masked tokens), idx_i2t int32 [Bg][Bg][I] (NULL: kept in the workspace).
+ * ws: ctclip_filip_ws_bytes(a) bytes (0 = unsupported shape; depends on which optional outputs are NULL),
+ * 16-B aligned: the two index arrays, A, C, the normalised tokens, their norms and 4 Bg floats -- with A and
+ * C passed in, at most 4 Bg^2 (T + I) + 4 Bg (T + I)(Dl + 2) + 64 KiB for every shape; it never grows
+ * with T * I.  1 <= Bg <= 128, 1 <= T <= 512, 1 <= I <= 1024, 16 <= Dl <= 512, Dl % 16 == 0: CT_ESHAPE
+ * otherwise, before any launch; a missing pointer or a short ws: CT_EINVAL; CT_EALIGN. */
+typedef struct {
+  const float* t_raw; const float* i_raw;
+  const uint8_t* mask;
+  const float* log_temp;
+  int32_t Bg, T, I, Dl;
+  int32_t decoupled, i2t_over_text;
+  float* loss; float* dt_raw; float* di_raw; float* dlogtemp;
+  float* A; float* C;                       /* optional */
+  int32_t* idx_t2i; int32_t* idx_i2t;       /* optional */
+  void* ws; int64_t ws_bytes;
+} ctclip_filip_args;
+int ctclip_filip_loss(const ctclip_filip_args* a, void* stream);
+int64_t ctclip_filip_ws_bytes(const ctclip_filip_args* a);
+
 #ifdef __cplusplus
 }
 #endif
