@@ -190,6 +190,16 @@ class FilipArgs(ctypes.Structure):
     ]
 
 
+class FilipScoresArgs(ctypes.Structure):
+    """ctclip_filip_scores_args (include/ctclip_hip.h): the rectangular token-wise scores, forward only."""
+    _fields_ = [
+        ('t_raw', c_vp), ('i_raw', c_vp), ('mask', c_vp), ('log_temp', c_vp),
+        ('R', c_i32), ('V', c_i32), ('T', c_i32), ('I', c_i32), ('Dl', c_i32), ('pad', c_i32),
+        ('A', c_vp), ('C', c_vp), ('idx_t2i', c_vp), ('val_t2i', c_vp),
+        ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 # name -> argtypes (restype is int32 unless _RESTYPES names another)
 _SIGS = {
     'ctclip_version': [],
@@ -327,6 +337,9 @@ _SIGS = {
     'ctclip_probe_step_ws_bytes': [ctypes.POINTER(ProbeArgs)],
     'ctclip_filip_loss': [ctypes.POINTER(FilipArgs), c_vp],
     'ctclip_filip_ws_bytes': [ctypes.POINTER(FilipArgs)],
+    'ctclip_filip_scores': [ctypes.POINTER(FilipScoresArgs), c_vp],
+    'ctclip_filip_scores_ws_bytes': [ctypes.POINTER(FilipScoresArgs)],
+    'ctclip_score_ranks': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     'ctclip_sgemm': [c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
                      c_i32, c_f32, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_vp],
     'ctclip_embed_fwd': [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -338,7 +351,8 @@ _SIGS = {
 }
 _RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_retrieval_ranks_ws_bytes': c_i64,
              'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64,
-             'ctclip_probe_step_ws_bytes': c_i64, 'ctclip_filip_ws_bytes': c_i64}
+             'ctclip_probe_step_ws_bytes': c_i64, 'ctclip_filip_ws_bytes': c_i64,
+             'ctclip_filip_scores_ws_bytes': c_i64}
 
 
 def register(name, argtypes):

@@ -1286,6 +1286,73 @@ def filip_loss(t_raw, i_raw, mask, log_temp, decoupled=False, i2t_over_text=Fals
     return res
 
 
+FILIP_SCORES_MAX_ROWS = 65535
+
+
+def filip_scores(t_raw, i_raw, mask, log_temp, want_idx=False):
+    """The token-wise scores of ``filip_loss``, forward only, for an unpaired rectangle (ctclip_filip_scores,
+    csrc/filip_eval.hip): t_raw [R, T, Dl] / i_raw [V, I, Dl] raw token latents, mask [R, T] uint8 / bool text
+    key mask, log_temp [1].  Returns a dict: A, C [R, V] f32 (text -> image, image -> text) and, with
+    ``want_idx``, idx_t2i int32 [R, V, T] (each kept text token's winning image token, the lowest index on ties,
+    -1 at masked tokens) and val_t2i f32 [R, V, T] (that winner's score, 0 at masked tokens).  The bits of
+    entry [x, y] depend only on report x and volume y: block-wise calls and one call over everything agree
+    bit for bit.  A report without a kept token raises ValueError (one host read)."""
+    if t_raw.dim() != 3 or i_raw.dim() != 3 or t_raw.shape[2] != i_raw.shape[2]:
+        raise ValueError(f'filip_scores: t_raw [R, T, Dl] / i_raw [V, I, Dl], got {tuple(t_raw.shape)} / '
+                         f'{tuple(i_raw.shape)}')
+    if t_raw.dtype != F32 or i_raw.dtype != F32 or log_temp.dtype != F32:
+        raise ValueError('filip_scores: f32 inputs')
+    R, T, Dl = t_raw.shape
+    V, I = i_raw.shape[:2]
+    if tuple(mask.shape) != (R, T) or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f'filip_scores: mask uint8 / bool {(R, T)}, got {mask.dtype} {tuple(mask.shape)}')
+    if i_raw.device != t_raw.device or mask.device != t_raw.device:
+        raise ValueError(f'filip_scores: t_raw on {t_raw.device}, i_raw on {i_raw.device}, mask on {mask.device}')
+    if R and T and not bool((mask != 0).any(1).all()):
+        raise ValueError('filip_scores: a report without a kept token (an all-zero mask row) has no score')
+    t_raw, i_raw, mask = t_raw.contiguous(), i_raw.contiguous(), mask.contiguous()
+    dev = t_raw.device
+    res = dict(A=torch.empty(R, V, device=dev, dtype=F32), C=torch.empty(R, V, device=dev, dtype=F32))
+    if want_idx:
+        res.update(idx_t2i=torch.empty(R, V, T, device=dev, dtype=torch.int32),
+                   val_t2i=torch.empty(R, V, T, device=dev, dtype=F32))
+    a = _lib.FilipScoresArgs(t_raw=ptr(t_raw), i_raw=ptr(i_raw), mask=ptr(mask), log_temp=ptr(log_temp), R=R, V=V,
+                             T=T, I=I, Dl=Dl, A=ptr(res['A']), C=ptr(res['C']), idx_t2i=ptr(res.get('idx_t2i')),
+                             val_t2i=ptr(res.get('val_t2i')))
+    nbytes = _lib.lib().ctclip_filip_scores_ws_bytes(_lib.ctypes.byref(a))
+    ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=F32)
+    a.ws, a.ws_bytes = ptr(ws), nbytes
+    call('ctclip_filip_scores', _lib.ctypes.byref(a), stream_ptr())
+    return res
+
+
+def score_ranks(S, pair=None):
+    """0-based rank [N] int32 of each query's positive gallery column ``pair[i]`` in a READY score matrix
+    S [N, M] f32 (ctclip_score_ranks): ``retrieval_ranks``' rule -- entries scoring higher rank above, and of
+    equal scores the lower gallery index.  ``pair=None``: the identity (needs N == M).  ``pair`` outside
+    [0, M) raises ValueError (one host read)."""
+    if S.dim() != 2:
+        raise ValueError(f'score_ranks: scores [N, M], got {tuple(S.shape)}')
+    _chk(S, 'score_ranks: scores', F32)
+    N, M = S.shape
+    if pair is None:
+        if N != M:
+            raise ValueError(f'score_ranks: pair=None pairs row i with column i, but N = {N} and M = {M}')
+        pair = torch.arange(N, device=S.device, dtype=torch.int32)
+    else:
+        if pair.dim() != 1 or pair.shape[0] != N or pair.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'score_ranks: pair must be {N} int32 / int64 gallery indices, got '
+                             f'{tuple(pair.shape)} {pair.dtype}')
+        _chk(pair, 'score_ranks: pair')
+        if N and (int(pair.min()) < 0 or int(pair.max()) >= M):
+            raise ValueError(f'score_ranks: pair entries must lie in [0, {M})')
+        pair = pair.to(device=S.device, dtype=torch.int32).contiguous()
+    S = S.contiguous()
+    rank = torch.empty(N, device=S.device, dtype=torch.int32)
+    call('ctclip_score_ranks', ptr(S), ptr(pair), N, M, ptr(rank), stream_ptr())
+    return rank
+
+
 PROBE_OUTPUTS = ('loss', 'dW', 'db', 'Z', 'count')
 
 

@@ -399,7 +399,8 @@ class CTClipTrainer:
         """The reference trainer's validation pass between steps (CTCLIPTrainer.py:356-454): score
         ``volumes`` zero-shot with ``classifier`` (a ``zero_shot.ZeroShotClassifier`` of this model
         with its prompts set -- the reference's are ``VALIDATION_PATHOLOGIES`` with
-        ``VALIDATION_TEMPLATE``; None: the one passed last time) and return
+        ``VALIDATION_TEMPLATE``; for a ``use_all_token_embeds`` model a
+        ``token_eval.TokenZeroShotClassifier``; None: the one passed last time) and return
         ``evaluate.ZeroShotEvaluator.evaluate``'s dict (probs, auroc, ci, f1_micro, flat_accuracy; with
         ``curves=True`` also ``curves`` -- operating point, threshold, PR-AUC, average precision per
         label -- and, with n_boot > 0, ``curves_ci``).
@@ -443,11 +444,17 @@ class CTClipTrainer:
         The contract is ``validate``'s: ``flush()`` first, a codebook EMA still pending afterwards
         raises, the forwards run in eval mode under ``no_grad``, the status word is saved, cleared,
         read and restored around the pass, ``EvalGuardError`` if the pass set any bit, the training
-        mode restored.  With world > 1 every rank calls it at the same step."""
-        from .retrieval import RetrievalEvaluator
+        mode restored.  With world > 1 every rank calls it at the same step.
+
+        A ``use_all_token_embeds`` model is ranked on its token-wise scores
+        (``token_eval.TokenRetrievalEvaluator``, direction 'mean'); the dict has the same keys."""
+        if getattr(self.model, 'use_all_token_embeds', False):
+            from .token_eval import TokenRetrievalEvaluator as Evaluator
+        else:
+            from .retrieval import RetrievalEvaluator as Evaluator
         return self._eval_pass('validate_retrieval', 'retrieval validation',
-                               lambda: RetrievalEvaluator(self.model).evaluate(volumes, text, pair=pair, ks=ks,
-                                                                               n_boot=n_boot, batch_size=batch_size))
+                               lambda: Evaluator(self.model).evaluate(volumes, text, pair=pair, ks=ks,
+                                                                      n_boot=n_boot, batch_size=batch_size))
 
     def attribute(self, volumes, classifier=None, **kw):
         """Zero-shot attribution maps between steps: ``classifier.attribute(volumes, **kw)``'s dict

@@ -984,6 +984,40 @@ typedef struct {
 int ctclip_filip_loss(const ctclip_filip_args* a, void* stream);
 int64_t ctclip_filip_ws_bytes(const ctclip_filip_args* a);
 
+/* ---------------------------------------------------------------- token-wise evaluation (csrc/filip_eval.hip)
+ * The scores of the fine-grained loss above, forward only, for an UNPAIRED rectangle of R reports x V volumes
+ * (zero-shot: 2P prompts x N volumes; retrieval: R reports x V volumes).  S, A and C as defined above:
+ *   A[x][y] = sum_t mask[x,t] max_i S / max(sum_t mask[x,t], 1e-6),   C[x][y] = (1 / I) sum_i max_{t kept} S.
+ * One exact-f32 product on the matrix pipe feeds both: a workgroup owns a whole (x, y) pair.  Only the KEPT
+ * text tokens are multiplied (a normalise pass compacts them per report, no host read).  S is never written.
+ * POSITION INVARIANCE: the bits of A[x][y], C[x][y], idx_t2i[x][y] and val_t2i[x][y] depend only on report x
+ * and volume y, not on R, V or the pair's place in the call, so block-wise and whole-matrix scoring agree
+ * bit for bit.  No float atomics, every sum in a fixed order: two runs give the same bits.
+ * t_raw [R][T][Dl], i_raw [V][I][Dl] f32 contiguous; mask [R][T] bytes (0 = padding; a row with none is
+ * memory-safe and meaningless); log_temp [1].  Outputs: A, C [R][V]; optional (NULL: not computed) idx_t2i
+ * int32 [R][V][T]: each kept text token's winning image token, the lowest index on ties, -1 at masked tokens;
+ * val_t2i f32 [R][V][T]: that winner's score, 0 at masked tokens.
+ * ws: ctclip_filip_scores_ws_bytes(a) bytes (0 = unsupported shape), 16-B aligned:
+ *   4 (R T Dl + V I Dl + up4(R) + up4(R T)), up4 = rounded up to a multiple of 4.
+ * 1 <= R, V <= 65535, 1 <= T <= 512, 1 <= I <= 1024, 16 <= Dl <= 512, Dl % 16 == 0: CT_ESHAPE otherwise,
+ * before any launch; a missing pointer or a short ws: CT_EINVAL; CT_EALIGN. */
+typedef struct {
+  const float* t_raw; const float* i_raw;
+  const uint8_t* mask;
+  const float* log_temp;
+  int32_t R, V, T, I, Dl, pad;
+  float* A; float* C;
+  int32_t* idx_t2i; float* val_t2i;         /* optional */
+  void* ws; int64_t ws_bytes;
+} ctclip_filip_scores_args;
+int ctclip_filip_scores(const ctclip_filip_scores_args* a, void* stream);
+int64_t ctclip_filip_scores_ws_bytes(const ctclip_filip_scores_args* a);
+/* rank [N] int32 from a READY score matrix S [N][M] f32 contiguous: the 0-based place of pair[i] (in [0, M),
+ * the caller's duty; an entry outside is read as column 0) in a stable descending sort of row i -- the rule
+ * of ctclip_retrieval_ranks: rank_i = #{ j != pair_i : S_ij > S_i,pair_i or (S_ij == S_i,pair_i and
+ * j < pair_i) }.  Integer counts, one wave per query.  N, M >= 1: CT_ESHAPE otherwise. */
+int ctclip_score_ranks(const float* S, const int32_t* pair, int32_t N, int32_t M, int32_t* rank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
