@@ -154,6 +154,16 @@ class ClipLossTiledArgs(ctypes.Structure):
     _fields_ = ClipLossExArgs._fields_[:-1] + [('ws_bytes', c_i64), ('grad_row0', c_i32), ('grad_rows', c_i32)]
 
 
+class SigmoidLossArgs(ctypes.Structure):
+    """ctclip_sigmoid_loss_args (include/ctclip_hip.h): the pairwise sigmoid contrastive loss."""
+    _fields_ = [
+        ('t_raw', c_vp), ('i_raw', c_vp), ('log_temp', c_vp), ('bias', c_vp),
+        ('Bg', c_i32), ('Dl', c_i32), ('grad_row0', c_i32), ('grad_rows', c_i32),
+        ('loss', c_vp), ('dt_raw', c_vp), ('di_raw', c_vp), ('dlogtemp', c_vp), ('dbias', c_vp),
+        ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 class MlmMaskArgs(ctypes.Structure):
     """ctclip_mlm_mask_args (include/ctclip_hip.h): the masked-language-model mask kernel."""
     _fields_ = [
@@ -316,6 +326,8 @@ _SIGS = {
     'ctclip_clip_loss_ex_ws_floats': [ctypes.POINTER(ClipLossExArgs)],
     'ctclip_clip_loss_tiled': [ctypes.POINTER(ClipLossTiledArgs), c_vp],
     'ctclip_clip_loss_tiled_ws_bytes': [ctypes.POINTER(ClipLossTiledArgs)],
+    'ctclip_sigmoid_loss': [ctypes.POINTER(SigmoidLossArgs), c_vp],
+    'ctclip_sigmoid_loss_ws_bytes': [ctypes.POINTER(SigmoidLossArgs)],
     'ctclip_clip_scores': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp],
     'ctclip_zero_shot': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     'ctclip_attr_weights': [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp],
@@ -349,7 +361,8 @@ _SIGS = {
     'ctclip_adam': [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_i32,
                     c_vp, c_vp],
 }
-_RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_retrieval_ranks_ws_bytes': c_i64,
+_RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_sigmoid_loss_ws_bytes': c_i64,
+             'ctclip_retrieval_ranks_ws_bytes': c_i64,
              'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64,
              'ctclip_probe_step_ws_bytes': c_i64, 'ctclip_filip_ws_bytes': c_i64,
              'ctclip_filip_scores_ws_bytes': c_i64}

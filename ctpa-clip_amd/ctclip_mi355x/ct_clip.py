@@ -14,6 +14,9 @@ Above 128 gathered rows both Functions take the tiled MFMA loss (``functional.se
 ``use_all_token_embeds`` (the fine-grained FILIP loss, :751-755,:829-843) takes a branch of its own,
 ``_forward_filip`` on ``functional.FilipLossFn`` (csrc/filip.hip): every report token
 against every spatial image token, one view, no extra projection, one rank.
+``sigmoid_loss=True`` (not in the reference) trains the pairwise sigmoid (SigLIP) loss instead of InfoNCE:
+``functional.SigmoidLossFn`` on csrc/loss_sigmoid.hip with a learned scalar ``logit_bias`` (DESIGN.md §30);
+one text and one image view, no extra projection, no DCL, no token-wise loss -- those combinations raise.
 ``aug_text`` (the reference itself cannot run it: it calls ``.shape`` on a BatchEncoding) and
 everything else raises.
 """
@@ -82,8 +85,21 @@ class CTCLIP(nn.Module):
                  decoupled_contrastive_learning=False, extra_latent_projection=False, use_mlm=False,
                  text_ssl_loss_weight=0.05, use_visual_ssl=False, visual_ssl=None, visual_ssl_type='simsiam',
                  visual_ssl_hidden_layer=-1, simclr_temperature=0.1, image_ssl_loss_weight=0.05,
-                 multiview_loss_weight=0.1, checkpoint_during_training=False, **kwargs):
+                 multiview_loss_weight=0.1, checkpoint_during_training=False, sigmoid_loss=False,
+                 sigmoid_bias_init=-10.0, sigmoid_temperature_init=None, **kwargs):
+        """``sigmoid_loss``: train the pairwise sigmoid loss (Zhai et al. 2023) instead of InfoNCE; the model
+        then owns a scalar parameter ``logit_bias`` (``sigmoid_bias_init``), absent otherwise, so the default
+        ``state_dict`` keys stay the reference's.  ``temperature`` (log scale) keeps its constructor value 1
+        unless ``sigmoid_temperature_init`` is given; the paper initialises temperature = log 10, bias = -10."""
         super().__init__()
+        if sigmoid_loss:
+            refused = dict(decoupled_contrastive_learning=decoupled_contrastive_learning,
+                           extra_latent_projection=extra_latent_projection,
+                           use_all_token_embeds=use_all_token_embeds)
+            for name, on in refused.items():
+                if on:
+                    raise NotImplementedError(f'CTCLIP: sigmoid_loss with {name} (the pairwise sigmoid loss has '
+                                              'one latent pair and no softmax denominator)')
         # use_all_token_embeds projects ONE spatial token of the image tower: the tower has to state its token
         # width (``.dim``, as CTViT does) and ``dim_image`` has to be that width.  With the flattened width
         # (h w d, the CLS configuration's) the pooled volume would be taken for a single token without an error
@@ -115,7 +131,11 @@ class CTCLIP(nn.Module):
         self.visual_transformer = image_encoder
         self.to_text_latent = nn.Linear(dim_text, dim_latent, bias=False)
         self.to_visual_latent = nn.Linear(dim_image, dim_latent, bias=False)
-        self.temperature = nn.Parameter(torch.tensor(1.))
+        self.temperature = nn.Parameter(torch.tensor(1. if sigmoid_temperature_init is None or not sigmoid_loss
+                                                     else float(sigmoid_temperature_init)))
+        self.sigmoid_loss = bool(sigmoid_loss)
+        if self.sigmoid_loss:
+            self.logit_bias = nn.Parameter(torch.tensor(float(sigmoid_bias_init)))
         self.extra_latent_projection = extra_latent_projection
         self.decoupled_contrastive_learning = decoupled_contrastive_learning
         self.to_text_latent_extra = copy.deepcopy(self.to_text_latent)
@@ -320,6 +340,9 @@ class CTCLIP(nn.Module):
                 raise NotImplementedError('CTCLIP: use_all_token_embeds with aug_image (the fine-grained loss has '
                                           'one image view)')
             return self._forward_filip(text, image, return_loss, return_encodings, return_latents)
+        if self.sigmoid_loss and aug_image is not None:
+            raise NotImplementedError('CTCLIP: sigmoid_loss with aug_image (the pairwise sigmoid loss has one '
+                                      'image view)')
         n_views = 1
         if aug_image is not None:
             aug = tuple(aug_image) if isinstance(aug_image, (tuple, list)) else (aug_image,)
@@ -358,8 +381,12 @@ class CTCLIP(nn.Module):
             from . import kernels as K
             if extra and not text_to_image:     # ct_clip.py:806: the image -> text latents
                 t_raw, i_raw = t_extra, i_extra
-            return K.clip_scores(t_raw.contiguous(), i_raw.contiguous(), self.temperature.detach().reshape(1))
+            scores = K.clip_scores(t_raw.contiguous(), i_raw.contiguous(), self.temperature.detach().reshape(1))
+            # sigmoid_loss: the logits the loss trains (the bias cancels in the evaluators' softmax / ranks)
+            return scores + self.logit_bias.detach() if self.sigmoid_loss else scores
         tg, self._t_gather = self._t_gather, None
+        if self.sigmoid_loss:
+            return Fn.SigmoidLossFn.apply(t_raw, i_raw, self.temperature, self.logit_bias, None, tg)
         if not general:
             return Fn.ClipLossFn.apply(t_raw, i_raw, self.temperature, None, tg)
         B, Dl = t_raw.shape

@@ -1334,6 +1334,46 @@ class ClipLossExFn(torch.autograd.Function):
         return dt * s, di * s, dtx, dix, (dlt * s * ctx.scale).reshape(()), None, None, None, None, None
 
 
+def sigmoid_loss_all_rows(t_raw, i_raw, log_temp, bias):
+    """The pairwise sigmoid loss of raw latents ``t_raw`` / ``i_raw`` [Bg, Dl] already on this device, with
+    the gradient of EVERY row from the one call: (loss [1], dt [Bg, Dl], di [Bg, Dl], dlog_temp [1],
+    dbias [1]).  The chunked step's loss over its latent caches (CTClipTrainer.train_step_chunked)."""
+    return K.sigmoid_loss(t_raw.contiguous(), i_raw.contiguous(), log_temp.detach().reshape(1).contiguous(),
+                          bias.detach().reshape(1).contiguous())
+
+
+class SigmoidLossFn(torch.autograd.Function):
+    """The pairwise sigmoid (SigLIP) contrastive loss on the fused ``kernels.sigmoid_loss``:
+    L = 1/Bg sum_ij softplus(-z_ij (exp(log_temp) <t^_i, i^_j> + bias)), z = +1 on the diagonal, -1 off it.
+    Under torch.distributed the raw latents are all-gathered as in ``ClipLossFn``; every rank computes the
+    same global loss and back-propagates its own rows (gradients are then SUM-reduced)."""
+
+    @staticmethod
+    def forward(ctx, t_raw, i_raw, log_temp, bias, impl=None, t_gather=None):
+        B = t_raw.shape[0]
+        tg, ig = dist_sync.gather_latents(t_raw, i_raw, t_gather)
+        lt, b = log_temp.detach().reshape(1).contiguous(), bias.detach().reshape(1).contiguous()
+        # impl: the fused HIP loss (default, this rank's rows only); tests substitute a CPU restatement that
+        # returns every row's gradient to exercise the exchange logic under gloo
+        if impl is None:
+            loss, dt, di, dlt, db = K.sigmoid_loss(tg.detach(), ig.detach(), lt, b,
+                                                   rows=(dist_sync.world_rank()[1] * B, B))
+        else:
+            loss, dt, di, dlt, db = impl(tg, ig, lt, b)[:5]
+            dt, di = dist_sync.local_rows(dt, B), dist_sync.local_rows(di, B)
+        ctx.save_for_backward(dt, di, dlt, db)
+        ctx.scale = dist_sync.replicated_grad_scale()
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dt, di, dlt, db = ctx.saved_tensors
+        s = dloss.reshape(1)
+        # log-temperature and bias gradients: every rank holds the full global value -> scaled by 1/world so
+        # the SUM all-reduce reproduces it once (see ClipLossFn)
+        return dt * s, di * s, (dlt * s * ctx.scale).reshape(()), (db * s * ctx.scale).reshape(()), None, None
+
+
 class FilipLossFn(torch.autograd.Function):
     """The fine-grained (FILIP) token-wise contrastive loss of ``use_all_token_embeds``
     (ct_clip/ct_clip.py:829-878) on the fused ``kernels.filip_loss``: ``t_raw`` [B, T, Dl] / ``i_raw``

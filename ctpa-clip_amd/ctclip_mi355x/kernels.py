@@ -1246,6 +1246,37 @@ def clip_loss_tiled(t_raw, i_raw, log_temp, t_extra=None, i_extra=None, decouple
     return loss, dt, di, dtx, dix, dlt, pair
 
 
+def sigmoid_loss(t_raw, i_raw, log_temp, bias, rows=None):
+    """The pairwise sigmoid (SigLIP) contrastive loss (ctclip_sigmoid_loss, csrc/loss_sigmoid.hip): t_raw /
+    i_raw [Bg, Dl] raw latents, log_temp [1], bias [1]; Bg and Dl up to 8192.  Returns (loss [1], dt, di,
+    dlt [1], dbias [1]); with ``rows=(row0, n)`` the latent gradients cover rows [row0, row0 + n) only and
+    come as [n, Dl] (loss, dlt and dbias stay the full global values)."""
+    if t_raw.dim() != 2 or i_raw.dim() != 2 or t_raw.shape != i_raw.shape:
+        raise ValueError(f'sigmoid_loss: two [Bg, Dl] latent sets, got {tuple(t_raw.shape)} / {tuple(i_raw.shape)}')
+    if log_temp.numel() != 1 or bias.numel() != 1:
+        raise ValueError('sigmoid_loss: log_temp and bias hold one element each')
+    if any(x.dtype != F32 for x in (t_raw, i_raw, log_temp, bias)):
+        raise ValueError('sigmoid_loss: f32 inputs')
+    if not all(x.is_contiguous() for x in (t_raw, i_raw, log_temp, bias)):
+        raise ValueError('sigmoid_loss: contiguous inputs')
+    Bg, Dl = t_raw.shape
+    row0, n = (0, Bg) if rows is None else (int(rows[0]), int(rows[1]))
+    if row0 < 0 or n < 1 or row0 + n > Bg:
+        raise ValueError(f'sigmoid_loss: rows {(row0, n)} outside the {Bg} global rows')
+    dev = t_raw.device
+    loss, dlt, dbias = (torch.empty(1, device=dev, dtype=F32) for _ in range(3))
+    dt = torch.empty(n, Dl, device=dev, dtype=F32)
+    di = torch.empty(n, Dl, device=dev, dtype=F32)
+    a = _lib.SigmoidLossArgs(t_raw=ptr(t_raw), i_raw=ptr(i_raw), log_temp=ptr(log_temp), bias=ptr(bias), Bg=Bg, Dl=Dl,
+                             grad_row0=row0, grad_rows=n, loss=ptr(loss), dt_raw=ptr(dt), di_raw=ptr(di),
+                             dlogtemp=ptr(dlt), dbias=ptr(dbias))
+    nbytes = _lib.lib().ctclip_sigmoid_loss_ws_bytes(_lib.ctypes.byref(a))
+    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=F32)
+    a.ws, a.ws_bytes = ptr(ws), nbytes
+    call('ctclip_sigmoid_loss', _lib.ctypes.byref(a), stream_ptr())
+    return loss, dt, di, dlt, dbias
+
+
 def filip_loss(t_raw, i_raw, mask, log_temp, decoupled=False, i2t_over_text=False, want_logits=False,
                want_idx=False):
     """The fine-grained (FILIP) token-wise contrastive loss (ctclip_filip_loss, csrc/filip.hip;

@@ -13,6 +13,7 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.clip_infonce(text_latents, image_latents, log_temp)
     torch.ops.ctclip.clip_infonce_ex(text_views, image_views, log_temp, text_extra, image_extra,
                                      decoupled, w_main, w_multiview)   # multiview / CLOOB / DCL loss
+    torch.ops.ctclip.sigmoid_loss(text_latents, image_latents, log_temp, bias)   # pairwise sigmoid (SigLIP)
     torch.ops.ctclip.retrieval_ranks(queries, gallery, pair)     # rank of each query's positive
     torch.ops.ctclip.retrieval_topk(queries, gallery, k)         # (score, idx) of the k best rows
     torch.ops.ctclip.vq_cos_argmax(x, codebook)                 # (idx int32, l2norm(x))
@@ -285,6 +286,44 @@ def clip_infonce_ex(text_latents: Tensor, image_latents: Tensor, log_temp: Tenso
     loss of pair 0 + w_multiview * mean of the other pairs (scalar)."""
     return _clip_infonce_ex(text_latents, image_latents, log_temp, text_extra, image_extra, bool(decoupled),
                             float(w_main), float(w_multiview))[0]
+
+
+# --------------------------------------------------------------------------- sigmoid_loss
+@torch.library.custom_op('ctclip::sigmoid_loss', mutates_args=(), device_types='cuda')
+def _sigmoid_loss(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor,
+                  bias: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    _need(text_latents.dtype == image_latents.dtype == log_temp.dtype == bias.dtype == F32, 'sigmoid_loss: f32 inputs')
+    _need(text_latents.shape == image_latents.shape and text_latents.dim() == 2, 'sigmoid_loss: [B, dim_latent]')
+    _need(log_temp.numel() == 1 and bias.numel() == 1, 'sigmoid_loss: log_temp and bias are scalars')
+    loss, dt, di, dlt, db = K.sigmoid_loss(text_latents.contiguous(), image_latents.contiguous(),
+                                           log_temp.reshape(1).contiguous(), bias.reshape(1).contiguous())
+    return loss.reshape(()), dt, di, dlt.reshape(log_temp.shape), db.reshape(bias.shape)
+
+
+@_sigmoid_loss.register_fake
+def _(text_latents, image_latents, log_temp, bias):
+    return (text_latents.new_empty(()), torch.empty_like(text_latents), torch.empty_like(image_latents),
+            torch.empty_like(log_temp), torch.empty_like(bias))
+
+
+def _sigmoid_setup(ctx, inputs, output):
+    _, dt, di, dlt, db = output
+    ctx.save_for_backward(dt, di, dlt, db)
+
+
+def _sigmoid_bwd(ctx, dloss, *_):
+    dt, di, dlt, db = ctx.saved_tensors
+    return dt * dloss, di * dloss, dlt * dloss, db * dloss
+
+
+_sigmoid_loss.register_autograd(_sigmoid_bwd, setup_context=_sigmoid_setup)
+
+
+def sigmoid_loss(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor, bias: Tensor) -> Tensor:
+    """The pairwise sigmoid (SigLIP) contrastive loss on raw latents [B, dim_latent]: l2-normalise both,
+    x = exp(log_temp) * t . i^T + bias, loss = sum_ij softplus(-z_ij x_ij) / B with z = +1 on the diagonal and
+    -1 off it (scalar)."""
+    return _sigmoid_loss(text_latents, image_latents, log_temp, bias)[0]
 
 
 # ------------------------------------------------------------------------------ retrieval

@@ -646,7 +646,8 @@ class CTClipTrainer:
         Three passes.  Pass 1 runs both towers per chunk under ``no_grad`` in train
         mode (BERT's dropout on, the codebook read and its EMA withheld) and writes the raw latents
         into two [1, Bg, Dl] caches.  One loss launch over the caches gives the loss, the gradient of
-        every cached row and of the temperature.  Pass 2 rewinds BERT's dropout call state to the one
+        every cached row and of the temperature (a ``sigmoid_loss`` model: the pairwise sigmoid loss,
+        ``functional.sigmoid_loss_all_rows``, and the gradient of ``logit_bias`` too).  Pass 2 rewinds BERT's dropout call state to the one
         recorded for the chunk, runs the chunk's training forward again and back-propagates its rows
         of the cached gradients; parameter gradients add up in the arena, the codebook's EMA
         statistics are held.  Then ONE ``optimizer_step``: one clip, one Adam, one skip word, one
@@ -770,8 +771,16 @@ class CTClipTrainer:
         try:
             with K.ln_guard():
                 tc, ic, states = self._chunked_pass1(text, video, chunk)
-                loss, dt, di, dlt = Fn.clip_loss_all_rows(tc, ic, model.temperature,
-                                                          bool(model.decoupled_contrastive_learning))
+                if getattr(model, 'sigmoid_loss', False):
+                    loss, dt, di, dlt, db = Fn.sigmoid_loss_all_rows(tc[0], ic[0], model.temperature,
+                                                                     model.logit_bias)
+                    if model.logit_bias.requires_grad:
+                        # as the temperature's below: the bias gradient of the one loss launch, once
+                        self.flat.rebind_grads([model.logit_bias])
+                        model.logit_bias.grad.add_(db.reshape(()))
+                else:
+                    loss, dt, di, dlt = Fn.clip_loss_all_rows(tc, ic, model.temperature,
+                                                              bool(model.decoupled_contrastive_learning))
                 if model.temperature.requires_grad:
                     # the temperature's gradient comes from the one loss launch, once
                     self.flat.rebind_grads([model.temperature])

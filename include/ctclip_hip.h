@@ -684,6 +684,29 @@ typedef struct {
 } ctclip_clip_loss_tiled_args;
 int ctclip_clip_loss_tiled(const ctclip_clip_loss_tiled_args* a, void* stream);
 int64_t ctclip_clip_loss_tiled_ws_bytes(const ctclip_clip_loss_tiled_args* a);
+/* The pairwise sigmoid (SigLIP) contrastive loss (csrc/loss_sigmoid.hip; Zhai et al. 2023), fused forward +
+ * backward, one text and one image view.  t_raw / i_raw [Bg][Dl] are raw projected latents; with both
+ * l2-normalised (eps 1e-12), temp = exp(*log_temp) and b = *bias:
+ *   x_ij = temp t_i . i_j + b,  z_ij = +1 (i = j) / -1,  *loss = 1/Bg sum_ij softplus(-z_ij x_ij),
+ * softplus(u) evaluated as max(u, 0) + log1p(exp(-|u|)).  Outputs: loss [1], dlogtemp [1], dbias [1] (always
+ * the full global values) and d loss / d raw of rows [grad_row0, grad_row0 + grad_rows) of both sets in
+ * [grad_rows][Dl] outputs (a row's bits do not depend on the range it was asked in).  The Bg x Bg logits and
+ * both gradient products run tiled on the f32 matrix pipe (exact f32); every sum has a fixed order: no float
+ * atomics, bit-reproducible.  ws: ctclip_sigmoid_loss_ws_bytes(a) bytes, 16-B aligned (0 = unsupported shape;
+ * 64-bit: d loss / d x of every pair is stored).  1 <= Bg <= 8192, 1 <= Dl <= 8192: CT_ESHAPE otherwise; a
+ * missing pointer, a short ws or a row range outside [0, Bg]: CT_EINVAL. */
+typedef struct {
+  const float* t_raw; const float* i_raw;
+  const float* log_temp; const float* bias;
+  int32_t Bg, Dl;
+  int32_t grad_row0, grad_rows;
+  float* loss;
+  float* dt_raw; float* di_raw;                 /* [grad_rows][Dl] each */
+  float* dlogtemp; float* dbias;
+  float* ws; int64_t ws_bytes;
+} ctclip_sigmoid_loss_args;
+int ctclip_sigmoid_loss(const ctclip_sigmoid_loss_args* a, void* stream);
+int64_t ctclip_sigmoid_loss_ws_bytes(const ctclip_sigmoid_loss_args* a);
 /* eval branch einsum('b d, b d -> b') * temp (ct_clip.py:805-807); with extra_latent_projection and
  * text_to_image = False the caller passes the extra latents (:806) */
 int ctclip_clip_scores(const float* t_raw, const float* i_raw, int32_t B, int32_t Dl, const float* log_temp,
