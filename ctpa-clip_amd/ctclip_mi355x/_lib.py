@@ -136,6 +136,17 @@ class EvalVolumeArgs(ctypes.Structure):
     ]
 
 
+class AugmentArgs(ctypes.Structure):
+    """ctclip_augment_args (include/ctclip_hip.h): the volume augmentation; ``recs`` points at
+    [V][B] device records of 16 8-byte words (12 matrix, gain, shift, sigma f64, seed u64)."""
+    _fields_ = [
+        ('src', c_vp), ('dtype', c_i32),
+        ('B', c_i64), ('D', c_i64), ('H', c_i64), ('W', c_i64),
+        ('V', c_i64),
+        ('recs', c_vp),
+    ]
+
+
 class ClipLossExArgs(ctypes.Structure):
     """ctclip_clip_loss_ex_args (include/ctclip_hip.h): the general contrastive loss."""
     _fields_ = [
@@ -334,6 +345,7 @@ _SIGS = {
     'ctclip_attr_map': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp],
     'ctclip_resample_volume': [ctypes.POINTER(ResampleArgs), c_vp, c_vp],
     'ctclip_eval_volume': [ctypes.POINTER(EvalVolumeArgs), c_vp, c_vp],
+    'ctclip_augment_volume': [ctypes.POINTER(AugmentArgs), c_vp, c_vp],
     'ctclip_auroc_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
     'ctclip_curve_boot': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
     'ctclip_retrieval_ranks_ws_bytes': [c_i32, c_i32, c_i32],

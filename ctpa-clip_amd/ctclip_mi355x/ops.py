@@ -16,6 +16,7 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.sigmoid_loss(text_latents, image_latents, log_temp, bias)   # pairwise sigmoid (SigLIP)
     torch.ops.ctclip.retrieval_ranks(queries, gallery, pair)     # rank of each query's positive
     torch.ops.ctclip.retrieval_topk(queries, gallery, k)         # (score, idx) of the k best rows
+    torch.ops.ctclip.augment_volume(video, records)              # [V, B, 1, D, H, W] augmented views
     torch.ops.ctclip.vq_cos_argmax(x, codebook)                 # (idx int32, l2norm(x))
     torch.ops.ctclip.peg_dwconv3d(x, weight, bias, shape, mode)  # x + PEG(x), canonical rows
     torch.ops.ctclip.cpb_mlp(rel, w0, b0, w1, b1, w2, b2)        # CPB table [heads, bins]
@@ -35,6 +36,7 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import augment as _augment
 from . import kernels as K
 
 BF16 = torch.bfloat16
@@ -350,6 +352,20 @@ def retrieval_topk(queries: Tensor, gallery: Tensor, k: int) -> Tuple[Tensor, Te
 @retrieval_topk.register_fake
 def _(queries, gallery, k):
     return queries.new_empty(queries.shape[0], k), queries.new_empty(queries.shape[0], k, dtype=torch.int32)
+
+
+# ------------------------------------------------------------------------- augment_volume
+@torch.library.custom_op('ctclip::augment_volume', mutates_args=(), device_types='cuda')
+def augment_volume(video: Tensor, records: Tensor) -> Tensor:
+    """[V, B, 1, D, H, W] augmented views of video (B, 1, D, H, W; int16 HU or f32) under the finite f64
+    records [V, B, 16] of ``augment.AugmentParams.pack`` (affine inverse map, gain, shift, noise level
+    and seed per view and sample), one launch.  Not differentiable (the input is data)."""
+    return _augment.augment_volume(video, records)
+
+
+@augment_volume.register_fake
+def _(video, records):
+    return video.new_empty((records.shape[0],) + tuple(video.shape))
 
 
 # -------------------------------------------------------------------------- vq_cos_argmax

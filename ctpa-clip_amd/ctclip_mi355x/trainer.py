@@ -619,6 +619,14 @@ class CTClipTrainer:
         loss.record_stream(caller)
         return loss
 
+    def train_step_augmented(self, text, video, augment, n_views=1):
+        """``train_step`` with ``n_views`` views of ``video`` made on the device by ``augment`` (an
+        ``augment.CTAugment``) as ``aug_image``.  The views are a function of (augment.seed,
+        self.steps, rank * B + b, view): a resumed run draws the same ones, ranks draw different ones."""
+        offset = dist_sync.world_rank()[1] * video.shape[0]
+        return self.train_step(text, video, aug_image=augment.views(video, step=self.steps, n_views=n_views,
+                                                                    sample_offset=offset))
+
     def _train_step(self, text, video, aug_image=None):
         self._check_ln(block_upto=self.steps - 2)
         self.model.train()

@@ -833,6 +833,34 @@ typedef struct {
 } ctclip_eval_volume_args;
 int ctclip_eval_volume(const ctclip_eval_volume_args* a, float* out, void* stream);
 
+/* ---------------------------------------------------------------- volume augmentation
+ * The views CTCLIP.forward(aug_image=...) takes: src (B, 1, D, H, W) contiguous,
+ * int16 HU or f32 in [-1, 1] (dtype CTCLIP_I16 / CTCLIP_F32) -> out [V][B][1][D][H][W] of the same
+ * dtype, every view of every sample in ONE launch.  recs [V][B] (device memory) holds per (view,
+ * sample) the inverse map [M | t] (row-major 3 x 4: output voxel o -> source coordinate
+ * M (o - c) + (c + t), c the volume centre, axes (d, h, w)), the intensity map gain / shift, the
+ * noise level sigma and the noise seed.  Trilinear taps outside the volume read -1 (the loader's
+ * pad value, in normalised units); y = clip(gain * x + shift + sigma * n, -1, 1) with n a
+ * zero-mean unit-variance Irwin-Hall(4) variate hashed from (seed, voxel index); int16 output is
+ * rint(1000 y).  All arithmetic is float64 in a fixed order without FMA contraction and rounded
+ * once (csrc/augment.hip states it operation by operation), so identity records return src bit
+ * for bit (HU inside [-1000, 1000]) and a float64 restatement reproduces every bit.  The records
+ * must be finite: the host checks (ctclip_mi355x/augment.py), the kernel does not.
+ * CT_ESHAPE: an extent < 1, V < 1, V * B > 65535, D > 65535, H * W >= 2^31.  Any element-aligned
+ * src / out. */
+typedef struct {
+  double m[12];             /* [M | t], row-major 3 x 4, rows (d, h, w) */
+  double gain, shift, sigma;
+  uint64_t seed;
+} ctclip_augment_rec;       /* 128 bytes */
+typedef struct {
+  const void* src; int32_t dtype;
+  int64_t B, D, H, W;
+  int64_t V;
+  const ctclip_augment_rec* recs;
+} ctclip_augment_args;
+int ctclip_augment_volume(const ctclip_augment_args* a, void* out, void* stream);
+
 /* ---------------------------------------------------------------- evaluation metrics
  * AUROC of S bootstrap resamples x P labels (ct_clip/evaluate.py:160-207 per resample of
  * evaluate.py:305-337): scores [N][P] f32, labels [N][P] uint8 (non-zero = positive), order [P][N]
