@@ -21,7 +21,8 @@ def _variants(K, fn):
     """Outputs of the 8-phase kernel (persistent, key 8) and the 128x256x32 kernel (key 1); the
     8-phase kernel with one workgroup per tile, persistent on a grid capped at 92 workgroups, and
     with its bf16 / GEGLU epilogue stores re-laid through LDS (ctclip_gemm_set_epi_lds), must match
-    the persistent one bit for bit."""
+    the persistent one bit for bit.  Those runs' outputs are handed back too (keys 'lds', 'lds_sc1',
+    'sc1', 'capped', 'single'), for tests that check every variant's whole buffer."""
     from ctclip_mi355x import _lib
     outs = {}
     lib = _lib.lib()
@@ -62,6 +63,7 @@ def _variants(K, fn):
         assert torch.equal(sc1, outs[8]), 'sc1 epilogue stores differ'
         assert torch.equal(single, outs[8]), 'persistent 8-phase GEMM differs from one workgroup per tile'
         assert torch.equal(capped, outs[8]), 'persistent 8-phase GEMM on a capped grid differs'
+    outs.update(lds=lds, lds_sc1=lds_sc1, sc1=sc1, capped=capped, single=single)
     return outs
 
 
