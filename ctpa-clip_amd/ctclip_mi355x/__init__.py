@@ -8,3 +8,4 @@ __version__ = '0.1.0'
 from . import ops  # noqa: E402,F401  (registers the torch.ops.ctclip.* custom ops)
 from .mlm import MLM  # noqa: E402,F401
 from .attribution import ZeroShotAttribution, to_volume  # noqa: E402,F401
+from .visual_ssl import VisualSSLHead  # noqa: E402,F401

@@ -175,6 +175,27 @@ class SigmoidLossArgs(ctypes.Structure):
     ]
 
 
+class SslLinearBnArgs(ctypes.Structure):
+    """ctclip_ssl_linear_bn_args (include/ctclip_hip.h): Linear + BatchNorm1d (+ ReLU) of the SimSiam head."""
+    _fields_ = [
+        ('X', c_vp), ('ldx', c_i64), ('W', c_vp), ('bias', c_vp), ('gamma', c_vp), ('beta', c_vp),
+        ('running_mean', c_vp), ('running_var', c_vp),
+        ('G', c_i32), ('R', c_i32), ('K', c_i64), ('N', c_i64),
+        ('relu', c_i32), ('use_running', c_i32), ('eps', c_f32), ('momentum', c_f32),
+        ('out', c_vp), ('xhat', c_vp), ('rstd', c_vp),
+    ]
+
+
+class SslBnBwdArgs(ctypes.Structure):
+    """ctclip_ssl_bn_bwd_args (include/ctclip_hip.h): its BatchNorm (+ ReLU) backward."""
+    _fields_ = [
+        ('dout', c_vp), ('out', c_vp), ('xhat', c_vp), ('rstd', c_vp), ('gamma', c_vp),
+        ('G', c_i32), ('R', c_i32), ('N', c_i64),
+        ('relu', c_i32), ('use_running', c_i32),
+        ('dy', c_vp), ('dgamma', c_vp), ('dbeta', c_vp), ('dbias', c_vp),
+    ]
+
+
 class MlmMaskArgs(ctypes.Structure):
     """ctclip_mlm_mask_args (include/ctclip_hip.h): the masked-language-model mask kernel."""
     _fields_ = [
@@ -339,6 +360,9 @@ _SIGS = {
     'ctclip_clip_loss_tiled_ws_bytes': [ctypes.POINTER(ClipLossTiledArgs)],
     'ctclip_sigmoid_loss': [ctypes.POINTER(SigmoidLossArgs), c_vp],
     'ctclip_sigmoid_loss_ws_bytes': [ctypes.POINTER(SigmoidLossArgs)],
+    'ctclip_ssl_linear_bn': [ctypes.POINTER(SslLinearBnArgs), c_vp],
+    'ctclip_ssl_bn_bwd': [ctypes.POINTER(SslBnBwdArgs), c_vp],
+    'ctclip_simsiam_loss': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
     'ctclip_clip_scores': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp],
     'ctclip_zero_shot': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     'ctclip_attr_weights': [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp],

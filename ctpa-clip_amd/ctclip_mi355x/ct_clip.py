@@ -17,6 +17,9 @@ against every spatial image token, one view, no extra projection, one rank.
 ``sigmoid_loss=True`` (not in the reference) trains the pairwise sigmoid (SigLIP) loss instead of InfoNCE:
 ``functional.SigmoidLossFn`` on csrc/loss_sigmoid.hip with a learned scalar ``logit_bias`` (DESIGN.md §30);
 one text and one image view, no extra projection, no DCL, no token-wise loss -- those combinations raise.
+``visual_ssl=VisualSSLHead(dim_latent)`` adds the SimSiam loss of the last two image views' raw latents with
+``image_ssl_loss_weight`` (visual_ssl.py, csrc/ssl.hip); ``use_visual_ssl=True`` without a head (the
+reference's built-in 2-D SimSiam / SimCLR) raises.
 ``aug_text`` (the reference itself cannot run it: it calls ``.shape`` on a BatchEncoding) and
 everything else raises.
 """
@@ -32,6 +35,7 @@ from torch import nn
 from . import dist_sync
 from . import functional as Fn
 from . import streams
+from .visual_ssl import VisualSSLHead
 
 
 # queue BERT's forward before the image tower's (A/B switch, default: image tower first)
@@ -105,9 +109,12 @@ class CTCLIP(nn.Module):
         # (h w d, the CLS configuration's) the pooled volume would be taken for a single token without an error
         token_width = getattr(image_encoder, 'dim', None)
         no_tokens = bool(use_all_token_embeds) and (token_width is None or int(token_width) != int(dim_image))
+        # visual self-supervision runs with a prebuilt VisualSSLHead only: the reference's built-in SimSiam /
+        # SimCLR (use_visual_ssl=True without a head) and any other visual_ssl object wrap a 2-D tower
+        head = visual_ssl if isinstance(visual_ssl, VisualSSLHead) else None
         unsupported = dict(use_all_token_embeds=no_tokens, downsample_image_embeds=downsample_image_embeds,
                            use_mlm=use_mlm,
-                           use_visual_ssl=use_visual_ssl or visual_ssl is not None,
+                           use_visual_ssl=(use_visual_ssl or visual_ssl is not None) and head is None,
                            text_causal_mask=text_causal_mask)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
@@ -141,7 +148,21 @@ class CTCLIP(nn.Module):
         self.to_text_latent_extra = copy.deepcopy(self.to_text_latent)
         self.to_visual_latent_extra = copy.deepcopy(self.to_visual_latent)
         self.multiview_loss_weight = multiview_loss_weight
-        self._wvis = {}                      # bf16 casts of the visual projections, a slot per weight
+        self.visual_ssl = None
+        if head is not None:
+            for name, on in dict(sigmoid_loss=sigmoid_loss, use_all_token_embeds=use_all_token_embeds).items():
+                if on:
+                    raise NotImplementedError(f'CTCLIP: visual_ssl with {name} (no image views there for the '
+                                              'self-supervised pair)')
+            if int(head.dim) != int(dim_latent):
+                raise ValueError(f'CTCLIP: the VisualSSLHead acts on the raw image latents, its dim {head.dim} '
+                                 f'must equal dim_latent {dim_latent}')
+            # registered only with a head, so the default state_dict keys stay the reference's.  The weight is
+            # image_ssl_loss_weight as given (the reference zeroes it unless use_visual_ssl is set too)
+            self.visual_ssl = head
+            self.image_ssl_loss_weight = float(image_ssl_loss_weight)
+            self.last_image_ssl_loss = None      # the detached [1] loss of the last forward, for logging
+        self._wvis = {}                    # bf16 casts of the visual projections, a slot per weight
         self.defer_text_backward = False     # set by CTClipTrainer (see encode)
         self._deferred_text = None
         self._deferred_image = None
@@ -355,6 +376,15 @@ class CTCLIP(nn.Module):
         assert not (self.multiview_loss_weight == 0 and is_multiview), \
             'multiview loss weight cannot be 0 if augmented text or images passed in'
         extra = self.extra_latent_projection
+        # visual self-supervision: the SimSiam head on the last two image views' raw latents
+        use_ssl = self.visual_ssl is not None and return_loss and not (return_latents or return_encodings)
+        if use_ssl:
+            if not is_multiview:
+                raise ValueError('CTCLIP: visual_ssl needs aug_image with return_loss (the self-supervised pair '
+                                 'is the last two image views)')
+            if dist_sync.world_rank()[0] > 1:
+                raise NotImplementedError('CTCLIP: visual_ssl under torch.distributed with world size > 1 (the '
+                                          'BatchNorm statistics and the 1 / world gradient scale are not defined)')
         if return_latents:
             enc_text = self.text_transformer(text.input_ids, attention_mask=text.attention_mask)[0]
             tokens = self.visual_transformer(image, return_encoded_tokens=True)
@@ -390,11 +420,19 @@ class CTCLIP(nn.Module):
         if not general:
             return Fn.ClipLossFn.apply(t_raw, i_raw, self.temperature, None, tg)
         B, Dl = t_raw.shape
-        w_mv = float(self.multiview_loss_weight) if is_multiview else 0.0   # ct_clip.py:886-890 (MLM / SSL weights 0)
-        return Fn.ClipLossExFn.apply(t_raw.view(1, B, Dl), i_raw.view(n_views, B, Dl),
+        w_mv = float(self.multiview_loss_weight) if is_multiview else 0.0   # ct_clip.py:886-890 (MLM weight 0)
+        w_ssl = self.image_ssl_loss_weight if use_ssl else 0.0
+        loss = Fn.ClipLossExFn.apply(t_raw.view(1, B, Dl), i_raw.view(n_views, B, Dl),
                                      t_extra.view(1, B, Dl) if extra else None,
                                      i_extra.view(n_views, B, Dl) if extra else None, self.temperature,
-                                     bool(self.decoupled_contrastive_learning), 1.0 - w_mv, w_mv, None, tg)
+                                     bool(self.decoupled_contrastive_learning), 1.0 - w_mv - w_ssl, w_mv, None, tg)
+        if use_ssl:
+            # (image, aug_1) with one augmented view, (aug_1, aug_2) with two; the gradient reaches
+            # to_visual_latent and the tower through i_raw (the leaf encode() makes under the trainer)
+            ssl = self.visual_ssl(i_raw.view(n_views, B, Dl)[-2:])
+            self.last_image_ssl_loss = ssl.detach().reshape(1)
+            loss = loss + w_ssl * ssl                                        # ct_clip.py:892-894
+        return loss
 
     def _forward_filip(self, text, image, return_loss, return_encodings, return_latents):
         """``use_all_token_embeds`` (ct_clip.py:751-755, 829-843): every report token against every spatial

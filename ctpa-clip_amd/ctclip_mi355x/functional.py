@@ -1374,6 +1374,76 @@ class SigmoidLossFn(torch.autograd.Function):
         return dt * s, di * s, (dlt * s * ctx.scale).reshape(()), (db * s * ctx.scale).reshape(()), None, None
 
 
+class LinearBNFn(torch.autograd.Function):
+    """Linear + BatchNorm1d (+ ReLU) of the SimSiam head on the fused ``kernels.ssl_linear_bn``:
+    ``x`` [G R, K] holds ``groups`` = G groups of R rows, each normalised on its own (one BatchNorm1d call of
+    the reference per view); ``running_mean`` / ``running_var`` are updated in place, group after group, unless
+    ``use_running`` (eval mode).  Backward: ``kernels.ssl_bn_bwd``, then dX = dy W and dW = dy^T X on
+    ``kernels.smm`` (exact f32, fixed order)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, gamma, beta, running_mean, running_var, groups, relu=False, eps=1e-5,
+                momentum=0.1, use_running=False):
+        det = lambda t: None if t is None else t.detach()
+        out, xhat, rstd = K.ssl_linear_bn(x.detach(), w.detach(), running_mean, running_var, groups=groups,
+                                          bias=det(bias), gamma=det(gamma), beta=det(beta), relu=relu, eps=eps,
+                                          momentum=momentum, use_running=use_running)
+        ctx.save_for_backward(x, w, out, xhat, rstd, gamma)
+        ctx.relu, ctx.use_running, ctx.has_bias = bool(relu), bool(use_running), bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w, out, xhat, rstd, gamma = ctx.saved_tensors
+        dy, dg, db, dbias = K.ssl_bn_bwd(dout.contiguous(), out if ctx.relu else None, xhat, rstd,
+                                         None if gamma is None else gamma.detach(), relu=ctx.relu,
+                                         use_running=ctx.use_running, want_affine=gamma is not None,
+                                         want_bias=ctx.has_bias)
+        dx = K.smm(dy, w.detach()) if ctx.needs_input_grad[0] else None
+        dw = K.smm(dy.t(), x.detach()) if ctx.needs_input_grad[1] else None
+        return dx, dw, dbias, dg, db, None, None, None, None, None, None, None
+
+
+class LinearBiasFn(torch.autograd.Function):
+    """y = x W^T + b in exact f32 (``kernels.linear_f32``): the SimSiam predictor's last Linear.  Backward on
+    ``kernels.smm``; db = 1^T dy is an smm too (one ascending chain per column)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        ctx.save_for_backward(x, w)
+        return K.linear_f32(x.detach().contiguous(), w.detach(), bias=bias.detach())[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = K.smm(dout, w.detach()) if ctx.needs_input_grad[0] else None
+        dw = K.smm(dout.t(), x.detach()) if ctx.needs_input_grad[1] else None
+        db = None
+        if ctx.needs_input_grad[2]:
+            db = K.smm(torch.ones(1, dout.shape[0], device=dout.device, dtype=dout.dtype), dout).reshape(-1)
+        return dx, dw, db
+
+
+class SimSiamLossFn(torch.autograd.Function):
+    """The SimSiam loss mean_b (2 - 2 cos(p1_b, z2_b)) + (2 - 2 cos(p2_b, z1_b)) on ``kernels.simsiam_loss``:
+    ``p1`` / ``p2`` [B, P] predictions, ``z1`` / ``z2`` targets (constants: no gradient, whatever they
+    require).  The kernel produces the gradients with the loss; backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, z1, z2):
+        loss, dp1, dp2 = K.simsiam_loss(p1.detach().contiguous(), p2.detach().contiguous(),
+                                        z1.detach().contiguous(), z2.detach().contiguous())
+        ctx.save_for_backward(dp1, dp2)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dp1, dp2 = ctx.saved_tensors
+        s = dloss.reshape(1)
+        return dp1 * s, dp2 * s, None, None
+
+
 class FilipLossFn(torch.autograd.Function):
     """The fine-grained (FILIP) token-wise contrastive loss of ``use_all_token_embeds``
     (ct_clip/ct_clip.py:829-878) on the fused ``kernels.filip_loss``: ``t_raw`` [B, T, Dl] / ``i_raw``

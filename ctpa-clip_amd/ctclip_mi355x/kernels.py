@@ -1277,6 +1277,87 @@ def sigmoid_loss(t_raw, i_raw, log_temp, bias, rows=None):
     return loss, dt, di, dlt, dbias
 
 
+def ssl_linear_bn(x, w, running_mean, running_var, *, groups, bias=None, gamma=None, beta=None, relu=False,
+                  eps=1e-5, momentum=0.1, use_running=False, out=None, xhat=None, rstd=None):
+    """Linear + BatchNorm1d (+ ReLU) in one launch (ctclip_ssl_linear_bn, csrc/ssl.hip): x [G R, K] f32 (any row
+    stride, unit column stride) holds ``groups`` = G groups of R consecutive rows, each one BatchNorm1d call;
+    w [N, K].  Returns (out, xhat [G R, N], rstd [G, N]); running_mean / running_var [N] are updated in place
+    for g = 0 .. G-1 in order unless ``use_running`` (eval mode), which normalises with them."""
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or x.shape[0] % max(int(groups), 1) != 0:
+        raise ValueError(f'ssl_linear_bn: x [G R, K], w [N, K], got {tuple(x.shape)} / {tuple(w.shape)}, G = {groups}')
+    M, Kd = x.shape
+    N, G = w.shape[0], int(groups)
+    for name, t, shape in (('bias', bias, (N,)), ('gamma', gamma, (N,)), ('beta', beta, (N,)),
+                           ('running_mean', running_mean, (N,)), ('running_var', running_var, (N,)),
+                           ('x', x, (M, Kd)), ('w', w, (N, Kd))):
+        if t is not None:
+            _chk(t, 'ssl_linear_bn: ' + name, F32)
+            if tuple(t.shape) != shape or (name != 'x' and not t.is_contiguous()):
+                raise ValueError(f'ssl_linear_bn: {name} must be a contiguous {shape} tensor')
+    if x.stride(1) != 1:
+        raise ValueError('ssl_linear_bn: x needs a unit column stride')
+    dev = x.device
+    out = torch.empty(M, N, device=dev, dtype=F32) if out is None else out
+    xhat = torch.empty(M, N, device=dev, dtype=F32) if xhat is None else xhat
+    rstd = torch.empty(G, N, device=dev, dtype=F32) if rstd is None else rstd
+    assert all(t.is_contiguous() and t.dtype == F32 for t in (out, xhat, rstd))
+    assert out.shape == (M, N) and xhat.shape == (M, N) and rstd.shape == (G, N)
+    a = _lib.SslLinearBnArgs(X=ptr(x), ldx=x.stride(0), W=ptr(w), bias=ptr(bias), gamma=ptr(gamma), beta=ptr(beta),
+                             running_mean=ptr(running_mean), running_var=ptr(running_var), G=G, R=M // max(G, 1),
+                             K=Kd, N=N, relu=int(relu), use_running=int(use_running), eps=float(eps),
+                             momentum=float(momentum), out=ptr(out), xhat=ptr(xhat), rstd=ptr(rstd))
+    call('ctclip_ssl_linear_bn', _lib.ctypes.byref(a), stream_ptr())
+    return out, xhat, rstd
+
+
+def ssl_bn_bwd(dout, out, xhat, rstd, gamma=None, *, relu=False, use_running=False, want_affine=False,
+               want_bias=False):
+    """The BatchNorm (+ ReLU) backward of ``ssl_linear_bn`` (ctclip_ssl_bn_bwd): dout, out, xhat [G R, N]
+    contiguous, rstd [G, N].  Returns (dy [G R, N], dgamma, dbeta, dbias [N]); dgamma / dbeta are None without
+    ``want_affine``, dbias (the column sums of dy) without ``want_bias``."""
+    if dout.dim() != 2 or rstd.dim() != 2 or xhat.shape != dout.shape or rstd.shape[1] != dout.shape[1] \
+            or rstd.shape[0] < 1 or dout.shape[0] % rstd.shape[0] != 0:
+        raise ValueError(f'ssl_bn_bwd: dout / xhat [G R, N], rstd [G, N], got {tuple(dout.shape)} / '
+                         f'{tuple(xhat.shape)} / {tuple(rstd.shape)}')
+    M, N = dout.shape
+    G = rstd.shape[0]
+    for name, t in (('dout', dout), ('out', out), ('xhat', xhat), ('rstd', rstd), ('gamma', gamma)):
+        if t is not None:
+            _chk(t, 'ssl_bn_bwd: ' + name, F32)
+            if not t.is_contiguous():
+                raise ValueError(f'ssl_bn_bwd: {name} must be contiguous')
+    if out is not None and out.shape != dout.shape:
+        raise ValueError('ssl_bn_bwd: out has the shape of dout')
+    dev = dout.device
+    dy = torch.empty(M, N, device=dev, dtype=F32)
+    dg, db = ((torch.empty(N, device=dev, dtype=F32) for _ in range(2)) if want_affine else (None, None))
+    dbias = torch.empty(N, device=dev, dtype=F32) if want_bias else None
+    a = _lib.SslBnBwdArgs(dout=ptr(dout), out=ptr(out), xhat=ptr(xhat), rstd=ptr(rstd), gamma=ptr(gamma), G=G,
+                          R=M // G, N=N, relu=int(relu), use_running=int(use_running), dy=ptr(dy), dgamma=ptr(dg),
+                          dbeta=ptr(db), dbias=ptr(dbias))
+    call('ctclip_ssl_bn_bwd', _lib.ctypes.byref(a), stream_ptr())
+    return dy, dg, db, dbias
+
+
+def simsiam_loss(p1, p2, z1, z2):
+    """The SimSiam loss and its gradient (ctclip_simsiam_loss, csrc/ssl.hip): p1, p2, z1, z2 [B, P] f32
+    contiguous, the z constants.  Returns (loss [1], dp1, dp2); B and P up to 8192."""
+    if p1.dim() != 2 or any(t.shape != p1.shape for t in (p2, z1, z2)):
+        raise ValueError(f'simsiam_loss: four [B, P] tensors, got {[tuple(t.shape) for t in (p1, p2, z1, z2)]}')
+    for t in (p1, p2, z1, z2):
+        _chk(t, 'simsiam_loss', F32)
+        if not t.is_contiguous():
+            raise ValueError('simsiam_loss: contiguous inputs')
+    B, P = p1.shape
+    dev = p1.device
+    loss = torch.empty(1, device=dev, dtype=F32)
+    dp1, dp2 = torch.empty_like(p1), torch.empty_like(p2)
+    ws = torch.empty(max(B, 1), device=dev, dtype=F32)
+    call('ctclip_simsiam_loss', ptr(p1), ptr(p2), ptr(z1), ptr(z2), B, P, ptr(loss), ptr(dp1), ptr(dp2), ptr(ws),
+         stream_ptr())
+    return loss, dp1, dp2
+
+
 def filip_loss(t_raw, i_raw, mask, log_temp, decoupled=False, i2t_over_text=False, want_logits=False,
                want_idx=False):
     """The fine-grained (FILIP) token-wise contrastive loss (ctclip_filip_loss, csrc/filip.hip;

@@ -4,6 +4,7 @@ from __future__ import annotations
 from .bert import BertConfig, BertModel
 from .ct_clip import CTCLIP
 from .ctvit import CTViT
+from .visual_ssl import VisualSSLHead
 
 BASE_VIT = dict(dim=512, codebook_size=8192, image_size=480, patch_size=20, temporal_patch_size=10,
                 spatial_depth=4, temporal_depth=4, dim_head=32, heads=8)
@@ -16,11 +17,19 @@ def build_ctclip(vit=None, bert=None, dim_latent=512, frames=240, **loss_options
     ``loss_options``: CTCLIP's decoupled_contrastive_learning / extra_latent_projection /
     multiview_loss_weight (default: the reference configuration, all off / 0.1) and
     use_all_token_embeds (the fine-grained token-wise loss: to_visual_latent then projects one
-    spatial token, so its input width is the ViT token width)."""
+    spatial token, so its input width is the ViT token width); ``visual_ssl=True`` or a dict of
+    ``VisualSSLHead`` options builds the SimSiam head on the raw image latents (with
+    ``image_ssl_loss_weight``)."""
     vk = dict(BASE_VIT)
     vk.update(vit or {})
     loss_options = dict(loss_options)
     all_tokens = bool(loss_options.pop('use_all_token_embeds', False))
+    # visual_ssl=True or a dict of VisualSSLHead options: the SimSiam head on the raw image latents
+    head = loss_options.pop('visual_ssl', None)
+    if head is True or isinstance(head, dict):
+        head = VisualSSLHead(dim_latent, **(head if isinstance(head, dict) else {}))
+    if head is not None and head is not False:
+        loss_options['visual_ssl'] = head
     image_encoder = CTViT(**vk, use_vgg_and_gan=False)
     text_encoder = BertModel(bert or BertConfig())
     grid = vk['image_size'] // vk['patch_size']

@@ -14,6 +14,9 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.clip_infonce_ex(text_views, image_views, log_temp, text_extra, image_extra,
                                      decoupled, w_main, w_multiview)   # multiview / CLOOB / DCL loss
     torch.ops.ctclip.sigmoid_loss(text_latents, image_latents, log_temp, bias)   # pairwise sigmoid (SigLIP)
+    torch.ops.ctclip.ssl_linear_bn(x, w, running_mean, running_var, groups, bias, gamma, beta, relu, eps,
+                                   momentum, use_running)        # Linear + BatchNorm1d (+ ReLU), SimSiam head
+    torch.ops.ctclip.simsiam_loss(p1, p2, z1, z2)                # SimSiam loss, targets z constant
     torch.ops.ctclip.retrieval_ranks(queries, gallery, pair)     # rank of each query's positive
     torch.ops.ctclip.retrieval_topk(queries, gallery, k)         # (score, idx) of the k best rows
     torch.ops.ctclip.augment_volume(video, records)              # [V, B, 1, D, H, W] augmented views
@@ -326,6 +329,86 @@ def sigmoid_loss(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor, 
     x = exp(log_temp) * t . i^T + bias, loss = sum_ij softplus(-z_ij x_ij) / B with z = +1 on the diagonal and
     -1 off it (scalar)."""
     return _sigmoid_loss(text_latents, image_latents, log_temp, bias)[0]
+
+
+# --------------------------------------------------------------------------- SimSiam head
+@torch.library.custom_op('ctclip::ssl_linear_bn', mutates_args=(), device_types='cuda')
+def _ssl_linear_bn(x: Tensor, w: Tensor, running_mean: Tensor, running_var: Tensor, groups: int,
+                   bias: Optional[Tensor] = None, gamma: Optional[Tensor] = None, beta: Optional[Tensor] = None,
+                   relu: bool = False, eps: float = 1e-5, momentum: float = 0.1,
+                   use_running: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    # functional: the kernel updates copies of the running statistics, returned as outputs 3 and 4
+    rm, rv = running_mean.clone(), running_var.clone()
+    out, xhat, rstd = K.ssl_linear_bn(x, w, rm, rv, groups=groups, bias=bias, gamma=gamma, beta=beta, relu=relu,
+                                      eps=eps, momentum=momentum, use_running=use_running)
+    return out, xhat, rstd, rm, rv
+
+
+@_ssl_linear_bn.register_fake
+def _(x, w, running_mean, running_var, groups, bias=None, gamma=None, beta=None, relu=False, eps=1e-5, momentum=0.1,
+      use_running=False):
+    M, N = x.shape[0], w.shape[0]
+    return (x.new_empty(M, N), x.new_empty(M, N), x.new_empty(groups, N), torch.empty_like(running_mean),
+            torch.empty_like(running_var))
+
+
+def _ssl_linear_bn_setup(ctx, inputs, output):
+    x, w, _, _, _, bias, gamma, _, relu, _, _, use_running = inputs
+    out, xhat, rstd = output[:3]
+    ctx.save_for_backward(x, w, out, xhat, rstd, gamma)
+    ctx.relu, ctx.use_running, ctx.has_bias = bool(relu), bool(use_running), bias is not None
+
+
+def _ssl_linear_bn_bwd(ctx, dout, *_):
+    x, w, out, xhat, rstd, gamma = ctx.saved_tensors
+    dy, dg, db, dbias = K.ssl_bn_bwd(dout.contiguous(), out if ctx.relu else None, xhat, rstd, gamma, relu=ctx.relu,
+                                     use_running=ctx.use_running, want_affine=gamma is not None,
+                                     want_bias=ctx.has_bias)
+    return K.smm(dy, w), K.smm(dy.t(), x), None, None, None, dbias, dg, db, None, None, None, None
+
+
+_ssl_linear_bn.register_autograd(_ssl_linear_bn_bwd, setup_context=_ssl_linear_bn_setup)
+
+
+def ssl_linear_bn(x: Tensor, w: Tensor, running_mean: Tensor, running_var: Tensor, groups: int,
+                  bias: Optional[Tensor] = None, gamma: Optional[Tensor] = None, beta: Optional[Tensor] = None,
+                  relu: bool = False, eps: float = 1e-5, momentum: float = 0.1,
+                  use_running: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """[relu](BatchNorm1d(x @ w^T (+ bias))) per group of x.shape[0] / groups consecutive rows in one launch,
+    exact f32 (at most 128 rows).  The op is functional: returns (out, running_mean, running_var), the running
+    statistics after the groups' updates in order (the given ones with ``use_running``, which normalises with
+    them)."""
+    r = _ssl_linear_bn(x, w, running_mean, running_var, groups, bias, gamma, beta, relu, eps, momentum, use_running)
+    return r[0], r[3], r[4]
+
+
+@torch.library.custom_op('ctclip::simsiam_loss', mutates_args=(), device_types='cuda')
+def _simsiam_loss(p1: Tensor, p2: Tensor, z1: Tensor, z2: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    loss, dp1, dp2 = K.simsiam_loss(p1.contiguous(), p2.contiguous(), z1.contiguous(), z2.contiguous())
+    return loss.reshape(()), dp1, dp2
+
+
+@_simsiam_loss.register_fake
+def _(p1, p2, z1, z2):
+    return p1.new_empty(()), torch.empty_like(p1), torch.empty_like(p2)
+
+
+def _simsiam_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1], output[2])
+
+
+def _simsiam_bwd(ctx, dloss, *_):
+    dp1, dp2 = ctx.saved_tensors
+    return dp1 * dloss, dp2 * dloss, None, None
+
+
+_simsiam_loss.register_autograd(_simsiam_bwd, setup_context=_simsiam_setup)
+
+
+def simsiam_loss(p1: Tensor, p2: Tensor, z1: Tensor, z2: Tensor) -> Tensor:
+    """The SimSiam loss mean_b (2 - 2 cos(p1_b, z2_b)) + (2 - 2 cos(p2_b, z1_b)) of predictions p and targets z
+    [B, P] (scalar); the targets are constants."""
+    return _simsiam_loss(p1, p2, z1, z2)[0]
 
 
 # ------------------------------------------------------------------------------ retrieval

@@ -671,6 +671,9 @@ class CTClipTrainer:
             raise NotImplementedError('train_step_chunked: extra_latent_projection=True is not chunked; use train_step')
         if getattr(self.model, 'use_all_token_embeds', False):
             raise NotImplementedError('train_step_chunked: use_all_token_embeds=True is not chunked; use train_step')
+        if getattr(self.model, 'visual_ssl', None) is not None:
+            raise NotImplementedError('train_step_chunked: visual_ssl is not chunked (its BatchNorm statistics are '
+                                      'one batch\'s); use train_step')
         if dist_sync.world_rank()[0] > 1:
             raise NotImplementedError('train_step_chunked: one rank only (the latent caches are not gathered '
                                       'across ranks yet)')

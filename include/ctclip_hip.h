@@ -707,6 +707,56 @@ typedef struct {
 } ctclip_sigmoid_loss_args;
 int ctclip_sigmoid_loss(const ctclip_sigmoid_loss_args* a, void* stream);
 int64_t ctclip_sigmoid_loss_ws_bytes(const ctclip_sigmoid_loss_args* a);
+/* The SimSiam visual self-supervision head (csrc/ssl.hip; Chen & He 2021).
+ *
+ * ctclip_ssl_linear_bn: Linear + BatchNorm1d (+ ReLU) in one launch.  X [G R][K] f32 (row stride ldx) holds G
+ * groups of R consecutive rows, one group = one BatchNorm1d call; W [N][K] f32 contiguous.
+ *   y = X W^T (+ bias)            exact f32 on the f32 matrix pipe, one ascending-k fma chain per output
+ *   per group g and feature n:    mean and BIASED variance of y over the group's R rows, rows ascending
+ *   xhat = (y - mean) rstd,  rstd = 1 / sqrt(var + eps),  out = [relu](gamma xhat + beta)
+ * gamma / beta: both or neither (neither: 1 / 0).  Outputs out [G R][N], xhat [G R][N], rstd [G][N], contiguous.
+ * running_mean / running_var [N] are updated for g = 0 .. G-1 in order, r <- (1 - momentum) r + momentum s with
+ * s the group's mean / UNBIASED variance (var R / (R - 1)): what G successive nn.BatchNorm1d calls leave.
+ * use_running (eval mode): mean / var are the running statistics for every group and nothing is updated.
+ * A workgroup owns 16 features and all rows; W is read once.  CT_ESHAPE: G R > 128, R < 2 without
+ * use_running, K % 4 != 0 or an extent < 1; CT_EINVAL: a missing pointer or half an affine pair; CT_EALIGN:
+ * ldx % 4 != 0, ldx < K or X / W not 16-B aligned. */
+typedef struct {
+  const float* X; int64_t ldx;
+  const float* W;
+  const float* bias;                             /* optional [N] */
+  const float* gamma; const float* beta;         /* optional [N], both or neither */
+  float* running_mean; float* running_var;       /* [N] */
+  int32_t G, R;
+  int64_t K, N;
+  int32_t relu, use_running;
+  float eps, momentum;
+  float* out; float* xhat; float* rstd;
+} ctclip_ssl_linear_bn_args;
+int ctclip_ssl_linear_bn(const ctclip_ssl_linear_bn_args* a, void* stream);
+/* Its backward up to the Linear: with mask = (out > 0) under relu (else 1) and gamma = 1 when absent,
+ *   dxhat = dout mask gamma,  dy = rstd / R (R dxhat - sum_r dxhat - xhat sum_r dxhat xhat)   per group,
+ *   use_running: dy = dxhat rstd.
+ * dy [G R][N]; dgamma = sum dout mask xhat, dbeta = sum dout mask, dbias = sum dy, each [N] and each written
+ * only where its pointer is given; the sums run over a group's rows ascending, then over the groups ascending.
+ * One thread per feature column.  out may be NULL without relu.  Shape rules as the forward's (no K). */
+typedef struct {
+  const float* dout; const float* out; const float* xhat; const float* rstd;
+  const float* gamma;                            /* optional [N] */
+  int32_t G, R;
+  int64_t N;
+  int32_t relu, use_running;
+  float* dy;
+  float* dgamma; float* dbeta; float* dbias;     /* optional [N] */
+} ctclip_ssl_bn_bwd_args;
+int ctclip_ssl_bn_bwd(const ctclip_ssl_bn_bwd_args* a, void* stream);
+/* The SimSiam loss, forward + backward: p1, p2 (predictions) and z1, z2 (targets, constants) [B][P] f32,
+ *   *loss = 1/B sum_b (2 - 2 cos(p1_b, z2_b)) + (2 - 2 cos(p2_b, z1_b)),  cos through x / max(|x|, 1e-12),
+ * dp1, dp2 [B][P] = d loss / d p (a clamped norm is a constant, as F.normalize's autograd has it: a zero row
+ * gives finite gradients).  One wave per row; the row terms are summed by one workgroup in a fixed order (no
+ * float atomics, bit-reproducible).  ws: B floats.  1 <= B <= 8192, 1 <= P <= 8192: CT_ESHAPE otherwise. */
+int ctclip_simsiam_loss(const float* p1, const float* p2, const float* z1, const float* z2, int32_t B, int32_t P,
+                        float* loss, float* dp1, float* dp2, float* ws, void* stream);
 /* eval branch einsum('b d, b d -> b') * temp (ct_clip.py:805-807); with extra_latent_projection and
  * text_to_image = False the caller passes the extra latents (:806) */
 int ctclip_clip_scores(const float* t_raw, const float* i_raw, int32_t B, int32_t Dl, const float* log_temp,
