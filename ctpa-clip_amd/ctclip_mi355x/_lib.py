@@ -175,6 +175,16 @@ class SigmoidLossArgs(ctypes.Structure):
     ]
 
 
+class MultiposLossArgs(ctypes.Structure):
+    """ctclip_multipos_loss_args (include/ctclip_hip.h): the multi-positive InfoNCE loss."""
+    _fields_ = [
+        ('t_raw', c_vp), ('i_raw', c_vp), ('ids', c_vp), ('log_temp', c_vp),
+        ('Bg', c_i32), ('Dl', c_i32), ('grad_row0', c_i32), ('grad_rows', c_i32),
+        ('loss', c_vp), ('dt_raw', c_vp), ('di_raw', c_vp), ('dlogtemp', c_vp), ('npos', c_vp),
+        ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 class SslLinearBnArgs(ctypes.Structure):
     """ctclip_ssl_linear_bn_args (include/ctclip_hip.h): Linear + BatchNorm1d (+ ReLU) of the SimSiam head."""
     _fields_ = [
@@ -360,6 +370,9 @@ _SIGS = {
     'ctclip_clip_loss_tiled_ws_bytes': [ctypes.POINTER(ClipLossTiledArgs)],
     'ctclip_sigmoid_loss': [ctypes.POINTER(SigmoidLossArgs), c_vp],
     'ctclip_sigmoid_loss_ws_bytes': [ctypes.POINTER(SigmoidLossArgs)],
+    'ctclip_multipos_loss': [ctypes.POINTER(MultiposLossArgs), c_vp],
+    'ctclip_multipos_loss_ws_bytes': [ctypes.POINTER(MultiposLossArgs)],
+    'ctclip_report_ids': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     'ctclip_ssl_linear_bn': [ctypes.POINTER(SslLinearBnArgs), c_vp],
     'ctclip_ssl_bn_bwd': [ctypes.POINTER(SslBnBwdArgs), c_vp],
     'ctclip_simsiam_loss': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -398,6 +411,7 @@ _SIGS = {
                     c_vp, c_vp],
 }
 _RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_sigmoid_loss_ws_bytes': c_i64,
+             'ctclip_multipos_loss_ws_bytes': c_i64,
              'ctclip_retrieval_ranks_ws_bytes': c_i64,
              'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64,
              'ctclip_probe_step_ws_bytes': c_i64, 'ctclip_filip_ws_bytes': c_i64,

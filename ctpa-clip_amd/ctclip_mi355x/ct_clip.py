@@ -17,6 +17,10 @@ against every spatial image token, one view, no extra projection, one rank.
 ``sigmoid_loss=True`` (not in the reference) trains the pairwise sigmoid (SigLIP) loss instead of InfoNCE:
 ``functional.SigmoidLossFn`` on csrc/loss_sigmoid.hip with a learned scalar ``logit_bias`` (DESIGN.md §30);
 one text and one image view, no extra projection, no DCL, no token-wise loss -- those combinations raise.
+``multi_positive=True`` (not in the reference) trains the duplicate-report-aware InfoNCE: the positives of a row
+are all rows of the global batch with its id -- ``forward(pair_ids=...)`` or, by default, a hash of the report's
+kept tokens made on the device (``kernels.report_ids``) -- on ``functional.MultiPosLossFn`` and
+csrc/loss_multipos.hip; one text and one image view, no other loss option.
 ``visual_ssl=VisualSSLHead(dim_latent)`` adds the SimSiam loss of the last two image views' raw latents with
 ``image_ssl_loss_weight`` (visual_ssl.py, csrc/ssl.hip); ``use_visual_ssl=True`` without a head (the
 reference's built-in 2-D SimSiam / SimCLR) raises.
@@ -90,12 +94,23 @@ class CTCLIP(nn.Module):
                  text_ssl_loss_weight=0.05, use_visual_ssl=False, visual_ssl=None, visual_ssl_type='simsiam',
                  visual_ssl_hidden_layer=-1, simclr_temperature=0.1, image_ssl_loss_weight=0.05,
                  multiview_loss_weight=0.1, checkpoint_during_training=False, sigmoid_loss=False,
-                 sigmoid_bias_init=-10.0, sigmoid_temperature_init=None, **kwargs):
+                 sigmoid_bias_init=-10.0, sigmoid_temperature_init=None, multi_positive=False, **kwargs):
         """``sigmoid_loss``: train the pairwise sigmoid loss (Zhai et al. 2023) instead of InfoNCE; the model
         then owns a scalar parameter ``logit_bias`` (``sigmoid_bias_init``), absent otherwise, so the default
         ``state_dict`` keys stay the reference's.  ``temperature`` (log scale) keeps its constructor value 1
-        unless ``sigmoid_temperature_init`` is given; the paper initialises temperature = log 10, bias = -10."""
+        unless ``sigmoid_temperature_init`` is given; the paper initialises temperature = log 10, bias = -10.
+        ``multi_positive``: InfoNCE whose positives are all pairs of one group (identical reports by default,
+        ``forward(pair_ids=)`` otherwise); no parameter and no ``state_dict`` key is added."""
         super().__init__()
+        if multi_positive:
+            refused = dict(sigmoid_loss=sigmoid_loss, decoupled_contrastive_learning=decoupled_contrastive_learning,
+                           extra_latent_projection=extra_latent_projection,
+                           use_all_token_embeds=use_all_token_embeds,
+                           visual_ssl=visual_ssl is not None)
+            for name, on in refused.items():
+                if on:
+                    raise NotImplementedError(f'CTCLIP: multi_positive with {name} (the multi-positive loss has '
+                                              'one latent pair and the plain softmax denominators)')
         if sigmoid_loss:
             refused = dict(decoupled_contrastive_learning=decoupled_contrastive_learning,
                            extra_latent_projection=extra_latent_projection,
@@ -143,6 +158,9 @@ class CTCLIP(nn.Module):
         self.sigmoid_loss = bool(sigmoid_loss)
         if self.sigmoid_loss:
             self.logit_bias = nn.Parameter(torch.tensor(float(sigmoid_bias_init)))
+        self.multi_positive = bool(multi_positive)
+        if self.multi_positive:
+            self.last_positive_count = None      # the detached [1] int32 npos of the last forward, for logging
         self.extra_latent_projection = extra_latent_projection
         self.decoupled_contrastive_learning = decoupled_contrastive_learning
         self.to_text_latent_extra = copy.deepcopy(self.to_text_latent)
@@ -349,13 +367,23 @@ class CTCLIP(nn.Module):
 
     def forward(self, text, image, device=None, return_loss=False, return_encodings=False, return_latents=False,
                 freeze_image_encoder=False, freeze_text_encoder=False, text_to_image=True, aug_text=None,
-                aug_image=None):
+                aug_image=None, pair_ids=None):
         """``CTCLIP.forward`` (ct_clip/ct_clip.py:614-901).  ``aug_image``: a tensor or a tuple of
         tensors shaped like ``image`` (int16 HU or f32), extra views of the same volumes: all views go
         through the image tower in one call (the VQ EMA sees them all, as in the reference) and each
-        view's contrastive loss is mixed in with ``multiview_loss_weight`` (:882-899)."""
+        view's contrastive loss is mixed in with ``multiview_loss_weight`` (:882-899).  ``pair_ids`` (a
+        ``multi_positive`` model with ``return_loss``): int64 [B] group ids, on host or device, global in
+        meaning -- every rank must agree on what an id names (a hash of an accession number, say); without
+        them the ids are ``kernels.report_ids`` of the reports.  ``last_positive_count`` then holds the
+        global number of ordered positive pairs off the diagonal ([1] int32, on the device)."""
         if aug_text is not None:
             raise NotImplementedError('multiview augmentation is off in the reference configuration')
+        if pair_ids is not None and not self.multi_positive:
+            raise ValueError('CTCLIP: pair_ids without multi_positive=True (the other losses take the diagonal '
+                             'as the only positives)')
+        if self.multi_positive and aug_image is not None:
+            raise NotImplementedError('CTCLIP: multi_positive with aug_image (the multi-positive loss has one '
+                                      'image view)')
         if self.use_all_token_embeds:
             if aug_image is not None:
                 raise NotImplementedError('CTCLIP: use_all_token_embeds with aug_image (the fine-grained loss has '
@@ -417,6 +445,18 @@ class CTCLIP(nn.Module):
         tg, self._t_gather = self._t_gather, None
         if self.sigmoid_loss:
             return Fn.SigmoidLossFn.apply(t_raw, i_raw, self.temperature, self.logit_bias, None, tg)
+        if self.multi_positive:
+            from . import kernels as K
+            B = t_raw.shape[0]
+            if pair_ids is None:
+                ids = K.report_ids(text.input_ids, text.attention_mask)
+            else:
+                if not torch.is_tensor(pair_ids) or pair_ids.dtype != torch.int64 or pair_ids.shape != (B,):
+                    raise ValueError(f'CTCLIP: pair_ids must be an int64 tensor [{B}]')
+                ids = pair_ids.to(t_raw.device).contiguous()
+            loss, npos = Fn.MultiPosLossFn.apply(t_raw, i_raw, ids, self.temperature, None, tg)
+            self.last_positive_count = npos.detach()
+            return loss
         if not general:
             return Fn.ClipLossFn.apply(t_raw, i_raw, self.temperature, None, tg)
         B, Dl = t_raw.shape

@@ -1374,6 +1374,52 @@ class SigmoidLossFn(torch.autograd.Function):
         return dt * s, di * s, (dlt * s * ctx.scale).reshape(()), (db * s * ctx.scale).reshape(()), None, None
 
 
+def multipos_loss_all_rows(t_raw, i_raw, ids, log_temp):
+    """The multi-positive InfoNCE loss of raw latents ``t_raw`` / ``i_raw`` [Bg, Dl] and group ids [Bg] (int64)
+    already on this device, with the gradient of EVERY row from the one call: (loss [1], dt [Bg, Dl],
+    di [Bg, Dl], dlog_temp [1], npos [1]).  The chunked step's loss over its latent caches
+    (CTClipTrainer.train_step_chunked)."""
+    return K.multipos_loss(t_raw.contiguous(), i_raw.contiguous(), ids.contiguous(),
+                           log_temp.detach().reshape(1).contiguous())
+
+
+class MultiPosLossFn(torch.autograd.Function):
+    """The multi-positive (duplicate-report-aware) InfoNCE loss on the fused ``kernels.multipos_loss``
+    (DESIGN.md §34): the positives of a row are all rows of the global batch that carry its id.  Under
+    torch.distributed the raw latents are all-gathered as in ``ClipLossFn`` and the int64 ids [B] -> [world B]
+    in the same global row order; every rank computes the same global loss and back-propagates its own rows
+    (gradients are then SUM-reduced).  Returns (loss, npos): npos [1] int32, the global count of ordered
+    positive pairs off the diagonal, carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, t_raw, i_raw, ids, log_temp, impl=None, t_gather=None):
+        B = t_raw.shape[0]
+        if ids.dtype != torch.int64 or ids.shape != (B,):
+            raise ValueError(f'MultiPosLossFn: ids must be int64 [{B}], got {ids.dtype} {tuple(ids.shape)}')
+        tg, ig = dist_sync.gather_latents(t_raw, i_raw, t_gather)
+        idg = dist_sync.finish_gather(dist_sync.start_gather(ids))
+        lt = log_temp.detach().reshape(1).contiguous()
+        # impl: the fused HIP loss (default, this rank's rows only); tests substitute a CPU restatement that
+        # returns every row's gradient to exercise the exchange logic under gloo
+        if impl is None:
+            loss, dt, di, dlt, npos = K.multipos_loss(tg.detach(), ig.detach(), idg, lt,
+                                                      rows=(dist_sync.world_rank()[1] * B, B))
+        else:
+            loss, dt, di, dlt, npos = impl(tg, ig, idg, lt)[:5]
+            dt, di = dist_sync.local_rows(dt, B), dist_sync.local_rows(di, B)
+        ctx.save_for_backward(dt, di, dlt)
+        ctx.scale = dist_sync.replicated_grad_scale()
+        ctx.mark_non_differentiable(npos)
+        return loss.reshape(()), npos
+
+    @staticmethod
+    def backward(ctx, dloss, _dnpos):
+        dt, di, dlt = ctx.saved_tensors
+        s = dloss.reshape(1)
+        # the log-temperature gradient is the full global value on every rank (see ClipLossFn)
+        return dt * s, di * s, None, (dlt * s * ctx.scale).reshape(()), None, None
+
+
 class LinearBNFn(torch.autograd.Function):
     """Linear + BatchNorm1d (+ ReLU) of the SimSiam head on the fused ``kernels.ssl_linear_bn``:
     ``x`` [G R, K] holds ``groups`` = G groups of R rows, each normalised on its own (one BatchNorm1d call of

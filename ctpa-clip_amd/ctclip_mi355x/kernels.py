@@ -1277,6 +1277,67 @@ def sigmoid_loss(t_raw, i_raw, log_temp, bias, rows=None):
     return loss, dt, di, dlt, dbias
 
 
+def multipos_loss(t_raw, i_raw, ids, log_temp, rows=None):
+    """The multi-positive InfoNCE loss (ctclip_multipos_loss, csrc/loss_multipos.hip): t_raw /
+    i_raw [Bg, Dl] raw latents, ids [Bg] int64 (rows with equal ids are positives of each other), log_temp [1];
+    Bg and Dl up to 8192.  Returns (loss [1], dt, di, dlt [1], npos [1] int32 = the number of ordered positive
+    pairs off the diagonal); with ``rows=(row0, n)`` the latent gradients cover rows [row0, row0 + n) only and
+    come as [n, Dl] (loss, dlt and npos stay the full global values)."""
+    if t_raw.dim() != 2 or i_raw.dim() != 2 or t_raw.shape != i_raw.shape:
+        raise ValueError(f'multipos_loss: two [Bg, Dl] latent sets, got {tuple(t_raw.shape)} / {tuple(i_raw.shape)}')
+    if log_temp.numel() != 1:
+        raise ValueError('multipos_loss: log_temp holds one element')
+    if any(x.dtype != F32 for x in (t_raw, i_raw, log_temp)):
+        raise ValueError('multipos_loss: f32 latents and log_temp')
+    Bg, Dl = t_raw.shape
+    if ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] != Bg:
+        raise ValueError(f'multipos_loss: ids must be int64 [{Bg}], got {ids.dtype} {tuple(ids.shape)}')
+    if not all(x.is_contiguous() for x in (t_raw, i_raw, ids, log_temp)):
+        raise ValueError('multipos_loss: contiguous inputs')
+    row0, n = (0, Bg) if rows is None else (int(rows[0]), int(rows[1]))
+    if row0 < 0 or n < 1 or row0 + n > Bg:
+        raise ValueError(f'multipos_loss: rows {(row0, n)} outside the {Bg} global rows')
+    dev = t_raw.device
+    loss, dlt = (torch.empty(1, device=dev, dtype=F32) for _ in range(2))
+    npos = torch.empty(1, device=dev, dtype=torch.int32)
+    dt = torch.empty(n, Dl, device=dev, dtype=F32)
+    di = torch.empty(n, Dl, device=dev, dtype=F32)
+    a = _lib.MultiposLossArgs(t_raw=ptr(t_raw), i_raw=ptr(i_raw), ids=ptr(ids), log_temp=ptr(log_temp), Bg=Bg, Dl=Dl,
+                              grad_row0=row0, grad_rows=n, loss=ptr(loss), dt_raw=ptr(dt), di_raw=ptr(di),
+                              dlogtemp=ptr(dlt), npos=ptr(npos))
+    nbytes = _lib.lib().ctclip_multipos_loss_ws_bytes(_lib.ctypes.byref(a))
+    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=F32)
+    a.ws, a.ws_bytes = ptr(ws), nbytes
+    call('ctclip_multipos_loss', _lib.ctypes.byref(a), stream_ptr())
+    return loss, dt, di, dlt, npos
+
+
+def report_ids(input_ids, attention_mask):
+    """One int64 id per report, on the device (ctclip_report_ids, csrc/loss_multipos.hip): input_ids /
+    attention_mask [B, L] integer tensors -> [B] int64.  Two rows get the same id exactly when their kept tokens
+    (``attention_mask != 0``) are the same sequence: pad content and anything behind the mask never matter,
+    length and position do.  The rule, every operation mod 2^64, on plain Python ints: with t_0 .. t_{n-1} the
+    kept tokens in order and ``m(x) = augment.mix64(x, 0)`` (the splitmix64 finaliser),
+
+        id = m( sum_k m( m(t_k) + (k + 1) * 0x9E3779B97F4A7C15 ) + n * 0xD1B54A32D192ED03 )
+
+    read as a signed 64-bit integer.  Integer arithmetic only and a commutative combine: the same on every
+    rank and every run.  Two different reports collide with probability 2^-64 (about Bg^2 / 2^65 for a batch)."""
+    if attention_mask is None:           # no mask: every token is kept
+        attention_mask = torch.ones_like(input_ids)
+    if input_ids.dim() != 2 or input_ids.shape != attention_mask.shape:
+        raise ValueError(f'report_ids: two [B, L] tensors, got {tuple(input_ids.shape)} / '
+                         f'{tuple(attention_mask.shape)}')
+    if input_ids.is_floating_point() or attention_mask.is_floating_point():
+        raise ValueError('report_ids: integer input_ids and attention_mask')
+    B, L = input_ids.shape
+    ids = input_ids.to(torch.int64).contiguous()
+    mask = attention_mask.to(torch.int64).contiguous()
+    out = torch.empty(B, device=ids.device, dtype=torch.int64)
+    call('ctclip_report_ids', ptr(ids), ptr(mask), B, L, ptr(out), stream_ptr())
+    return out
+
+
 def ssl_linear_bn(x, w, running_mean, running_var, *, groups, bias=None, gamma=None, beta=None, relu=False,
                   eps=1e-5, momentum=0.1, use_running=False, out=None, xhat=None, rstd=None):
     """Linear + BatchNorm1d (+ ReLU) in one launch (ctclip_ssl_linear_bn, csrc/ssl.hip): x [G R, K] f32 (any row

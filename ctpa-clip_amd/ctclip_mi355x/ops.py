@@ -14,6 +14,7 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.clip_infonce_ex(text_views, image_views, log_temp, text_extra, image_extra,
                                      decoupled, w_main, w_multiview)   # multiview / CLOOB / DCL loss
     torch.ops.ctclip.sigmoid_loss(text_latents, image_latents, log_temp, bias)   # pairwise sigmoid (SigLIP)
+    torch.ops.ctclip.multipos_loss(text_latents, image_latents, ids, log_temp)   # multi-positive InfoNCE
     torch.ops.ctclip.ssl_linear_bn(x, w, running_mean, running_var, groups, bias, gamma, beta, relu, eps,
                                    momentum, use_running)        # Linear + BatchNorm1d (+ ReLU), SimSiam head
     torch.ops.ctclip.simsiam_loss(p1, p2, z1, z2)                # SimSiam loss, targets z constant
@@ -329,6 +330,45 @@ def sigmoid_loss(text_latents: Tensor, image_latents: Tensor, log_temp: Tensor, 
     x = exp(log_temp) * t . i^T + bias, loss = sum_ij softplus(-z_ij x_ij) / B with z = +1 on the diagonal and
     -1 off it (scalar)."""
     return _sigmoid_loss(text_latents, image_latents, log_temp, bias)[0]
+
+
+# --------------------------------------------------------------------------- multipos_loss
+@torch.library.custom_op('ctclip::multipos_loss', mutates_args=(), device_types='cuda')
+def _multipos_loss(text_latents: Tensor, image_latents: Tensor, ids: Tensor,
+                   log_temp: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    _need(text_latents.dtype == image_latents.dtype == log_temp.dtype == F32, 'multipos_loss: f32 latents and log_temp')
+    _need(text_latents.shape == image_latents.shape and text_latents.dim() == 2, 'multipos_loss: [B, dim_latent]')
+    _need(ids.dtype == torch.int64 and ids.shape == text_latents.shape[:1], 'multipos_loss: ids int64 [B]')
+    _need(log_temp.numel() == 1, 'multipos_loss: log_temp is a scalar')
+    loss, dt, di, dlt, npos = K.multipos_loss(text_latents.contiguous(), image_latents.contiguous(),
+                                              ids.contiguous(), log_temp.reshape(1).contiguous())
+    return loss.reshape(()), dt, di, dlt.reshape(log_temp.shape), npos
+
+
+@_multipos_loss.register_fake
+def _(text_latents, image_latents, ids, log_temp):
+    return (text_latents.new_empty(()), torch.empty_like(text_latents), torch.empty_like(image_latents),
+            torch.empty_like(log_temp), text_latents.new_empty((1,), dtype=torch.int32))
+
+
+def _multipos_setup(ctx, inputs, output):
+    _, dt, di, dlt, _ = output
+    ctx.save_for_backward(dt, di, dlt)
+
+
+def _multipos_bwd(ctx, dloss, *_):
+    dt, di, dlt = ctx.saved_tensors
+    return dt * dloss, di * dloss, None, dlt * dloss
+
+
+_multipos_loss.register_autograd(_multipos_bwd, setup_context=_multipos_setup)
+
+
+def multipos_loss(text_latents: Tensor, image_latents: Tensor, ids: Tensor, log_temp: Tensor) -> Tensor:
+    """The multi-positive InfoNCE loss on raw latents [B, dim_latent] and int64 group ids [B]: l2-normalise
+    both, x = exp(log_temp) * t . i^T, the positives of a row are all rows with its id; the mean over both
+    directions of logsumexp - mean of the positives' logits (scalar)."""
+    return _multipos_loss(text_latents, image_latents, ids, log_temp)[0]
 
 
 # --------------------------------------------------------------------------- SimSiam head

@@ -253,13 +253,15 @@ class CTClipTrainer:
     def _fold_bucket(self, tag):
         self.flat.rebind_grads(self.bucket_params.get(tag, ()))
 
-    def forward_backward(self, text, video, aug_image=None):
+    def forward_backward(self, text, video, aug_image=None, pair_ids=None):
         self.grad_sync.arm()
         defer = hasattr(self.model, 'backward_deferred_text')
         if defer:
             self.model.defer_text_backward = True
         try:
             kw = {} if aug_image is None else dict(aug_image=aug_image)   # extra image views (multiview)
+            if pair_ids is not None:
+                kw['pair_ids'] = pair_ids                                  # a multi_positive model's group ids
             loss = self.model(text, video, device=self.device, return_loss=True, **kw)
             loss.backward()                      # the loss node (both towers' latents are leaves)
             if defer:
@@ -601,20 +603,21 @@ class CTClipTrainer:
                skip=self.skip_ring[st % 4:st % 4 + 1] if self._guard else None)
         self.flat.sync_shadows(off, off + n)
 
-    def train_step(self, text, video, aug_image=None):
+    def train_step(self, text, video, aug_image=None, pair_ids=None):
         """One contrastive step; returns the loss tensor (no host sync).  ``aug_image``: augmented
-        views of ``video`` for the multiview loss (CTCLIP.forward).  Raises
+        views of ``video`` for the multiview loss (CTCLIP.forward); ``pair_ids``: the int64 [B] group ids
+        of a ``multi_positive`` model (default: a hash of each report, made on the device).  Raises
         LayerNormExchangeError once the status copy of an earlier step shows a timed-out LayerNorm
         exchange (at the latest two steps later; ``check()`` / ``flush()`` wait for all)."""
         hp = streams.main_stream(self.device)
         if hp is None:
-            return self._train_step(text, video, aug_image)
+            return self._train_step(text, video, aug_image, pair_ids)
         # CTCLIP_MAIN_PRIORITY=1: the step on the high-priority stream, ordered after the caller's
         # work so far, and the caller's stream after it
         caller = torch.cuda.current_stream(self.device)
         hp.wait_stream(caller)
         with torch.cuda.stream(hp):
-            loss = self._train_step(text, video, aug_image)
+            loss = self._train_step(text, video, aug_image, pair_ids)
         caller.wait_stream(hp)
         loss.record_stream(caller)
         return loss
@@ -627,7 +630,7 @@ class CTClipTrainer:
         return self.train_step(text, video, aug_image=augment.views(video, step=self.steps, n_views=n_views,
                                                                     sample_offset=offset))
 
-    def _train_step(self, text, video, aug_image=None):
+    def _train_step(self, text, video, aug_image=None, pair_ids=None):
         self._check_ln(block_upto=self.steps - 2)
         self.model.train()
         own = hasattr(self.model, 'ema_after_step')
@@ -635,7 +638,7 @@ class CTClipTrainer:
             self.model.ema_after_step = True     # the codebook EMA goes after optimizer_step
         try:
             with K.ln_guard():
-                loss = self.forward_backward(text, video, aug_image)
+                loss = self.forward_backward(text, video, aug_image, pair_ids)
         finally:
             if own:
                 self.model.ema_after_step = False
@@ -644,7 +647,7 @@ class CTClipTrainer:
         return loss.detach()
 
     # ------------------------------------------------------------------ chunked step
-    def train_step_chunked(self, text, video, chunk, aug_image=None):
+    def train_step_chunked(self, text, video, chunk, aug_image=None, pair_ids=None):
         """One contrastive step on ``Bg = len(video)`` pairs whose towers run ``chunk`` pairs at a time
         (the last chunk may be shorter): the loss and every gradient are those of the ONE batch of Bg
         pairs -- each row's negatives are all the others -- while only one chunk's activations are
@@ -655,7 +658,9 @@ class CTClipTrainer:
         mode (BERT's dropout on, the codebook read and its EMA withheld) and writes the raw latents
         into two [1, Bg, Dl] caches.  One loss launch over the caches gives the loss, the gradient of
         every cached row and of the temperature (a ``sigmoid_loss`` model: the pairwise sigmoid loss,
-        ``functional.sigmoid_loss_all_rows``, and the gradient of ``logit_bias`` too).  Pass 2 rewinds BERT's dropout call state to the one
+        ``functional.sigmoid_loss_all_rows``, and the gradient of ``logit_bias`` too; a ``multi_positive``
+        model: ``functional.multipos_loss_all_rows`` on ``pair_ids`` [Bg] or, without them, on the chunks'
+        ``kernels.report_ids`` concatenated beside the caches).  Pass 2 rewinds BERT's dropout call state to the one
         recorded for the chunk, runs the chunk's training forward again and back-propagates its rows
         of the cached gradients; parameter gradients add up in the arena, the codebook's EMA
         statistics are held.  Then ONE ``optimizer_step``: one clip, one Adam, one skip word, one
@@ -685,13 +690,18 @@ class CTClipTrainer:
         Bg = int(video.shape[0])
         if int(text.input_ids.shape[0]) != Bg or Bg < 1:
             raise ValueError(f'train_step_chunked: {int(text.input_ids.shape[0])} reports for {Bg} volumes')
+        if pair_ids is not None:
+            if not getattr(self.model, 'multi_positive', False):
+                raise ValueError('train_step_chunked: pair_ids without a multi_positive model')
+            if not torch.is_tensor(pair_ids) or pair_ids.dtype != torch.int64 or pair_ids.shape != (Bg,):
+                raise ValueError(f'train_step_chunked: pair_ids must be an int64 tensor [{Bg}]')
         hp = streams.main_stream(self.device)
         if hp is None:
-            return self._train_step_chunked(text, video, chunk)
+            return self._train_step_chunked(text, video, chunk, pair_ids)
         caller = torch.cuda.current_stream(self.device)
         hp.wait_stream(caller)
         with torch.cuda.stream(hp):
-            loss = self._train_step_chunked(text, video, chunk)
+            loss = self._train_step_chunked(text, video, chunk, pair_ids)
         caller.wait_stream(hp)
         loss.record_stream(caller)
         return loss
@@ -710,10 +720,11 @@ class CTClipTrainer:
         tt = getattr(self.model, 'text_transformer', None)
         return getattr(tt, 'dropout_state', None), getattr(tt, 'set_dropout_state', None)
 
-    def _chunked_pass1(self, text, video, chunk):
+    def _chunked_pass1(self, text, video, chunk, ids_out=None):
         """Pass 1 of ``train_step_chunked``: (text cache, image cache [1, Bg, Dl] f32 raw latents,
         BERT's dropout call state at the start of every chunk).  Train mode, no autograd graph, the
-        codebook EMA withheld: the codebook and its cluster sizes are left as they were."""
+        codebook EMA withheld: the codebook and its cluster sizes are left as they were.  ``ids_out``: a
+        list that receives every chunk's ``kernels.report_ids`` (a ``multi_positive`` model's default ids)."""
         model = self.model
         model.train()
         get, _ = self._dropout_hooks()
@@ -725,6 +736,8 @@ class CTClipTrainer:
                 for r0, r1, t, v in self._chunks(text, video, chunk):
                     states.append(get() if get is not None else None)
                     _, _, t_raw, i_raw = model.encode(t, v)
+                    if ids_out is not None:
+                        ids_out.append(K.report_ids(t.input_ids, t.attention_mask))
                     if tc is None:
                         Bg = int(video.shape[0])
                         tc = torch.empty(1, Bg, t_raw.shape[1], device=self.device, dtype=torch.float32)
@@ -768,7 +781,7 @@ class CTClipTrainer:
             model.defer_text_backward = False
             model.set_ema_mode(old)
 
-    def _train_step_chunked(self, text, video, chunk):
+    def _train_step_chunked(self, text, video, chunk, pair_ids=None):
         from . import functional as Fn
         self._check_ln(block_upto=self.steps - 2)
         model = self.model
@@ -781,8 +794,14 @@ class CTClipTrainer:
         dist_sync.disarm()
         try:
             with K.ln_guard():
-                tc, ic, states = self._chunked_pass1(text, video, chunk)
-                if getattr(model, 'sigmoid_loss', False):
+                multipos = getattr(model, 'multi_positive', False)
+                hashed = [] if multipos and pair_ids is None else None
+                tc, ic, states = self._chunked_pass1(text, video, chunk, hashed)
+                if multipos:
+                    ids = torch.cat(hashed) if pair_ids is None else pair_ids.to(self.device)
+                    loss, dt, di, dlt, npos = Fn.multipos_loss_all_rows(tc[0], ic[0], ids, model.temperature)
+                    model.last_positive_count = npos
+                elif getattr(model, 'sigmoid_loss', False):
                     loss, dt, di, dlt, db = Fn.sigmoid_loss_all_rows(tc[0], ic[0], model.temperature,
                                                                      model.logit_bias)
                     if model.logit_bias.requires_grad:

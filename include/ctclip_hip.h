@@ -707,6 +707,42 @@ typedef struct {
 } ctclip_sigmoid_loss_args;
 int ctclip_sigmoid_loss(const ctclip_sigmoid_loss_args* a, void* stream);
 int64_t ctclip_sigmoid_loss_ws_bytes(const ctclip_sigmoid_loss_args* a);
+/* The multi-positive (duplicate-report-aware) InfoNCE loss (csrc/loss_multipos.hip),
+ * fused forward + backward, one text and one image view.  t_raw / i_raw [Bg][Dl] are raw projected latents,
+ * ids [Bg] one int64 group id per global row; with both sets l2-normalised (eps 1e-12), temp = exp(*log_temp),
+ * x_ij = temp t_i . i_j, P_i = { j : ids_j == ids_i } and n_i = |P_i|:
+ *   *loss = 1/2Bg [ sum_i (logsumexp_j x_ij - 1/n_i sum_{j in P_i} x_ij)
+ *                 + sum_j (logsumexp_i x_ij - 1/n_j sum_{i in P_j} x_ij) ],   *npos = sum_i (n_i - 1),
+ * every logsumexp carried as (max, sum exp(x - max)) so it is finite for any temp.  Outputs: loss [1],
+ * dlogtemp [1], npos [1] (always the full global values) and d loss / d raw of rows [grad_row0, grad_row0 +
+ * grad_rows) of both sets in [grad_rows][Dl] outputs (a row's bits do not depend on the range it was asked
+ * in).  The Bg x Bg logits and both gradient products run tiled on the f32 matrix pipe (exact f32); every sum
+ * has a fixed order: no float atomics, bit-reproducible.  ws: ctclip_multipos_loss_ws_bytes(a) bytes, 16-B
+ * aligned (0 = unsupported shape; 64-bit: the logits, then d loss / d x, of every pair are stored).
+ * 1 <= Bg <= 8192, 1 <= Dl <= 8192: CT_ESHAPE otherwise; a missing pointer, a short ws or a row range outside
+ * [0, Bg]: CT_EINVAL; a ws off 16 bytes: CT_EALIGN. */
+typedef struct {
+  const float* t_raw; const float* i_raw;
+  const int64_t* ids;                           /* [Bg] */
+  const float* log_temp;
+  int32_t Bg, Dl;
+  int32_t grad_row0, grad_rows;
+  float* loss;
+  float* dt_raw; float* di_raw;                 /* [grad_rows][Dl] each */
+  float* dlogtemp;
+  int32_t* npos;
+  float* ws; int64_t ws_bytes;
+} ctclip_multipos_loss_args;
+int ctclip_multipos_loss(const ctclip_multipos_loss_args* a, void* stream);
+int64_t ctclip_multipos_loss_ws_bytes(const ctclip_multipos_loss_args* a);
+/* One 64-bit id per report, on the device (csrc/loss_multipos.hip): input_ids / attention_mask [B][L] int64,
+ * out [B] int64.  With t_0 .. t_{n-1} the tokens whose mask is non-zero, in order, m the splitmix64 finaliser
+ * and every operation mod 2^64:
+ *   out = m( sum_k m( m(t_k) + (k + 1) 0x9E3779B97F4A7C15 ) + n 0xD1B54A32D192ED03 )
+ * so two rows share an id exactly (up to a 2^-64 collision) when their kept tokens are the same sequence; pad
+ * content never matters.  1 <= B, 1 <= L <= 2^20: CT_ESHAPE otherwise; a missing pointer: CT_EINVAL. */
+int ctclip_report_ids(const int64_t* input_ids, const int64_t* attention_mask, int32_t B, int32_t L, int64_t* out,
+                      void* stream);
 /* The SimSiam visual self-supervision head (csrc/ssl.hip; Chen & He 2021).
  *
  * ctclip_ssl_linear_bn: Linear + BatchNorm1d (+ ReLU) in one launch.  X [G R][K] f32 (row stride ldx) holds G
