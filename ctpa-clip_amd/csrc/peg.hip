@@ -813,7 +813,8 @@ size_t wgrad_smem(int W) { return std::max<size_t>((size_t)NSLOT * plane_bytes(W
 bool s_tile_attr = false;
 void tile_attrs() {
   if (s_tile_attr) return;
-  // up to W = 30: 4 x 4 x 32 x 128 B + weights = 72 KB
+  // tiled_ok stops at W = 24 (the one-item-per-thread budgets TNTH and WNTH; the plane alone would hold W = 30):
+  // 3 slots x 4 rows x 26 columns x 128 B + weights = 47 KB, under the 80 KB asked for
   const void* ks[] = {(const void*)peg_tile_kernel<0>,         (const void*)peg_tile_kernel<1>,
                       (const void*)peg_tile_kernel<0, 24, 0>,  (const void*)peg_tile_kernel<0, 24, 1>,
                       (const void*)peg_tile_kernel<1, 24, 0>,  (const void*)peg_tile_kernel<1, 24, 1>,

@@ -144,7 +144,7 @@ def test_peg_canonical_walk_matches_view_walk(K):
 @pytest.mark.parametrize('shape,D', [((2, 6, 5, 7), 128),      # plane-streaming path, ragged h tile / w segment
                                      ((1, 24, 24, 24), 512),   # base token grid (480^2 x 240 volume)
                                      ((2, 24, 24, 24), 128),   # two volumes (mode 1: canonical walk)
-                                     ((1, 3, 4, 40), 64),      # W > 30: general path
+                                     ((1, 3, 4, 40), 64),      # W > 24 (tiled_ok's limit): general path
                                      ((2, 2, 3, 4), 24)])      # D % 64 != 0: general path
 def test_peg(K, mode, shape, D):
     torch.manual_seed(2)
