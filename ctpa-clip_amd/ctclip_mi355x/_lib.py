@@ -389,6 +389,9 @@ _SIGS = {
     'ctclip_retrieval_ranks': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'ctclip_retrieval_topk_ws_bytes': [c_i32, c_i32, c_i32, c_i32],
     'ctclip_retrieval_topk': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
+    'ctclip_case_retrieval_ws_bytes': [c_i32, c_i32, c_i32, c_i32],
+    'ctclip_case_retrieval': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32,
+                              c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     'ctclip_mlm_mask': [ctypes.POINTER(MlmMaskArgs), c_vp],
     'ctclip_mlm_gather': [c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'ctclip_mlm_ce_ws_bytes': [c_i32],
@@ -413,7 +416,8 @@ _SIGS = {
 _RESTYPES = {'ctclip_clip_loss_tiled_ws_bytes': c_i64, 'ctclip_sigmoid_loss_ws_bytes': c_i64,
              'ctclip_multipos_loss_ws_bytes': c_i64,
              'ctclip_retrieval_ranks_ws_bytes': c_i64,
-             'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_mlm_ce_ws_bytes': c_i64,
+             'ctclip_retrieval_topk_ws_bytes': c_i64, 'ctclip_case_retrieval_ws_bytes': c_i64,
+             'ctclip_mlm_ce_ws_bytes': c_i64,
              'ctclip_probe_step_ws_bytes': c_i64, 'ctclip_filip_ws_bytes': c_i64,
              'ctclip_filip_scores_ws_bytes': c_i64}
 

@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import types
 
 import torch
 
@@ -1720,6 +1721,81 @@ def retrieval_topk(q, g, k):
     ws = torch.empty(max(nbytes // 4, 4), device=q.device, dtype=F32)
     call('ctclip_retrieval_topk', ptr(q), ptr(g), N, M, Dl, k, ptr(score), ptr(idx), ptr(ws), nbytes, stream_ptr())
     return score, idx
+
+
+CASE_RETRIEVAL_MAX_KS = 8
+CASE_RETRIEVAL_REL = {'any': 0, 'exact': 1}
+
+
+def _case_vec(name, what, t, n, dtype):
+    if t.dim() != 1 or t.shape[0] != n or t.dtype != dtype:
+        raise ValueError(f'case_retrieval: {name} must be {what} [{n}] {dtype}, got {tuple(t.shape)} {t.dtype}')
+
+
+def case_retrieval(q, g, qlab, glab, qgrp=None, ggrp=None, ks=(1, 5, 10, 50), rel='any'):
+    """Label-graded volume-to-volume retrieval in one fused pass (ctclip_case_retrieval; the header has the
+    definitions): raw f32 latents q [N, Dl] / g [M, Dl] (may be one tensor), int64 label bitmasks qlab [N] /
+    glab [M] (``retrieval.pack_labels``), int32 group ids qgrp [N] / ggrp [M] or neither (gallery row j is
+    invisible to query i iff qgrp[i] >= 0 and ggrp[j] == qgrp[i]), ``ks`` strictly ascending (at most 8,
+    the last at most 128), ``rel`` 'any' or 'exact'.
+
+    Returns a namespace: ``idx`` / ``score`` [N, K_max] (int32 / f32; unfilled places -1 / 0), ``filled`` [N]
+    and ``nrel`` [N] int32, ``hits`` [N, len(ks)] int32, ``ap`` and ``gain`` [N, len(ks)] f64 (``ap`` -1
+    where a query has no relevant visible row; ``gain`` the undivided Jaccard sum), and ``ks``.
+
+    Everything the host can see is refused with ValueError before the library is touched; N, M > 65,536 or
+    Dl > 8,192 raise KernelError (CT_ESHAPE)."""
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1] or 0 in q.shape or 0 in g.shape:
+        raise ValueError(f'case_retrieval: queries [N, Dl] and gallery [M, Dl], got {tuple(q.shape)} / '
+                         f'{tuple(g.shape)}')
+    if q.dtype != F32 or g.dtype != F32:
+        raise ValueError(f'case_retrieval: latents must be float32, got {q.dtype} / {g.dtype}')
+    N, Dl = q.shape
+    M = g.shape[0]
+    _case_vec('qlab', 'label bitmasks', qlab, N, torch.int64)
+    _case_vec('glab', 'label bitmasks', glab, M, torch.int64)
+    if (qgrp is None) != (ggrp is None):
+        raise ValueError('case_retrieval: qgrp and ggrp come together (group ids of the queries and of the gallery)')
+    if qgrp is not None:
+        _case_vec('qgrp', 'group ids', qgrp, N, torch.int32)
+        _case_vec('ggrp', 'group ids', ggrp, M, torch.int32)
+    try:
+        ks = [int(k) for k in ks]
+    except TypeError:
+        raise ValueError(f'case_retrieval: ks must be a sequence of integers, got {ks!r}') from None
+    if (not 1 <= len(ks) <= CASE_RETRIEVAL_MAX_KS or ks[0] < 1 or ks[-1] > RETRIEVAL_MAX_K
+            or any(b <= a for a, b in zip(ks, ks[1:]))):
+        raise ValueError(f'case_retrieval: ks must be 1 to {CASE_RETRIEVAL_MAX_KS} strictly ascending values in '
+                         f'[1, {RETRIEVAL_MAX_K}] (K above {RETRIEVAL_MAX_K} is not supported), got {ks}')
+    if rel not in CASE_RETRIEVAL_REL:
+        raise ValueError(f"case_retrieval: rel must be 'any' or 'exact', got {rel!r} (graded relevance is always "
+                         "the Jaccard gain; nDCG is not provided)")
+    tensors = dict(queries=q, gallery=g, qlab=qlab, glab=glab)
+    if qgrp is not None:
+        tensors.update(qgrp=qgrp, ggrp=ggrp)
+    for name, t in tensors.items():
+        if not t.is_contiguous():
+            raise ValueError(f'case_retrieval: {name} must be contiguous')
+    for name, t in tensors.items():
+        _chk(t, f'case_retrieval: {name}')
+        if t.device != q.device:
+            raise ValueError(f'case_retrieval: queries on {q.device}, {name} on {t.device}')
+    nK, kmax = len(ks), ks[-1]
+    dev = q.device
+    out = types.SimpleNamespace(
+        idx=torch.empty(N, kmax, device=dev, dtype=torch.int32), score=torch.empty(N, kmax, device=dev, dtype=F32),
+        filled=torch.empty(N, device=dev, dtype=torch.int32), nrel=torch.empty(N, device=dev, dtype=torch.int32),
+        hits=torch.empty(N, nK, device=dev, dtype=torch.int32),
+        ap=torch.empty(N, nK, device=dev, dtype=torch.float64),
+        gain=torch.empty(N, nK, device=dev, dtype=torch.float64), ks=tuple(ks))
+    nbytes = 0
+    if N <= RETRIEVAL_MAX_ROWS and M <= RETRIEVAL_MAX_ROWS and Dl <= RETRIEVAL_MAX_DIM:
+        nbytes = _lib.lib().ctclip_case_retrieval_ws_bytes(N, M, Dl, kmax)
+    ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=F32)
+    call('ctclip_case_retrieval', ptr(q), ptr(g), ptr(qlab), ptr(glab), ptr(qgrp), ptr(ggrp), N, M, Dl,
+         (_lib.c_i32 * nK)(*ks), nK, CASE_RETRIEVAL_REL[rel], ptr(out.idx), ptr(out.score), ptr(out.filled),
+         ptr(out.nrel), ptr(out.hits), ptr(out.ap), ptr(out.gain), ptr(ws), nbytes, stream_ptr())
+    return out
 
 
 # ----------------------------------------------------------------------------- masked language modelling

@@ -20,6 +20,7 @@ are the same kernels exposed one operation at a time, for callers that compose t
     torch.ops.ctclip.simsiam_loss(p1, p2, z1, z2)                # SimSiam loss, targets z constant
     torch.ops.ctclip.retrieval_ranks(queries, gallery, pair)     # rank of each query's positive
     torch.ops.ctclip.retrieval_topk(queries, gallery, k)         # (score, idx) of the k best rows
+    torch.ops.ctclip.case_retrieval(queries, gallery, qlab, glab, qgrp, ggrp, ks, rel)   # label-graded MAP@K
     torch.ops.ctclip.augment_volume(video, records)              # [V, B, 1, D, H, W] augmented views
     torch.ops.ctclip.vq_cos_argmax(x, codebook)                 # (idx int32, l2norm(x))
     torch.ops.ctclip.peg_dwconv3d(x, weight, bias, shape, mode)  # x + PEG(x), canonical rows
@@ -475,6 +476,25 @@ def retrieval_topk(queries: Tensor, gallery: Tensor, k: int) -> Tuple[Tensor, Te
 @retrieval_topk.register_fake
 def _(queries, gallery, k):
     return queries.new_empty(queries.shape[0], k), queries.new_empty(queries.shape[0], k, dtype=torch.int32)
+
+
+@torch.library.custom_op('ctclip::case_retrieval', mutates_args=(), device_types='cuda')
+def case_retrieval(queries: Tensor, gallery: Tensor, qlab: Tensor, glab: Tensor, qgrp: Optional[Tensor],
+                   ggrp: Optional[Tensor], ks: List[int],
+                   rel: str = 'any') -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(idx, score, filled, nrel, hits, ap, gain) of ``kernels.case_retrieval``: each query's ks[-1] best
+    visible gallery rows and their label-graded hits@K / AP@K / Jaccard gain@K, one fused pass.  Not
+    differentiable."""
+    r = K.case_retrieval(queries, gallery, qlab, glab, qgrp, ggrp, ks, rel)
+    return r.idx, r.score, r.filled, r.nrel, r.hits, r.ap, r.gain
+
+
+@case_retrieval.register_fake
+def _(queries, gallery, qlab, glab, qgrp, ggrp, ks, rel='any'):
+    N, nK, i32 = queries.shape[0], len(ks), torch.int32
+    return (queries.new_empty(N, ks[-1], dtype=i32), queries.new_empty(N, ks[-1]), queries.new_empty(N, dtype=i32),
+            queries.new_empty(N, dtype=i32), queries.new_empty(N, nK, dtype=i32),
+            queries.new_empty(N, nK, dtype=torch.float64), queries.new_empty(N, nK, dtype=torch.float64))
 
 
 # ------------------------------------------------------------------------- augment_volume

@@ -458,6 +458,25 @@ class CTClipTrainer:
                                lambda: Evaluator(self.model).evaluate(volumes, text, pair=pair, ks=ks,
                                                                       n_boot=n_boot, batch_size=batch_size))
 
+    def validate_case_retrieval(self, volumes, labels, groups=None, **kw):
+        """Volume-to-volume retrieval scored by pathology labels between steps:
+        ``retrieval.CaseRetrievalEvaluator(model).evaluate(volumes, labels, groups, **kw)``'s dict (the lists,
+        MAP@K, precision@K, mean Jaccard@K, bootstrap CIs with n_boot > 0, and the latents).
+
+        The contract is ``validate``'s: ``flush()`` first, a codebook EMA still pending afterwards
+        raises, the forwards run in eval mode under ``no_grad``, the status word is saved, cleared,
+        read and restored around the pass, ``EvalGuardError`` if the pass set any bit, the training
+        mode restored.  With world > 1 every rank calls it at the same step; each rank ranks what it was
+        passed (the gallery is not sharded), and the pass adds no collective.
+
+        A ``use_all_token_embeds`` model is refused (``ct_clip.require_cls_latents``): token-wise case
+        retrieval is not provided."""
+        from .ct_clip import require_cls_latents
+        from .retrieval import CaseRetrievalEvaluator
+        require_cls_latents(self.model, 'CTClipTrainer.validate_case_retrieval')
+        return self._eval_pass('validate_case_retrieval', 'case retrieval validation',
+                               lambda: CaseRetrievalEvaluator(self.model).evaluate(volumes, labels, groups, **kw))
+
     def attribute(self, volumes, classifier=None, **kw):
         """Zero-shot attribution maps between steps: ``classifier.attribute(volumes, **kw)``'s dict
         (maps, probs, scores; ``attribution.ZeroShotAttribution.maps``) with the prompts encoded again

@@ -998,6 +998,41 @@ int64_t ctclip_retrieval_topk_ws_bytes(int32_t N, int32_t M, int32_t Dl, int32_t
 int ctclip_retrieval_topk(const float* q, const float* g, int32_t N, int32_t M, int32_t Dl, int32_t k, float* score,
                           int32_t* idx, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- case retrieval (csrc/case_retrieval.hip)
+ * Volume-to-volume retrieval scored by pathology labels: each query's K_max best VISIBLE gallery rows and,
+ * from their labels, hits@K, AP@K and the graded (Jaccard) gain@K, in one pass that never writes N x M.
+ *   q [N][Dl], g [M][Dl]: raw f32 latents (may be one buffer: normalised once then).  Scores S_ij exactly as
+ *     ctclip_retrieval_topk makes them (the same normalisation, the same MFMA chain in ascending k), so an
+ *     entry's bits depend only on its two rows.
+ *   qlab [N], glab [M]: int64 bitmasks of up to 64 labels (bit c = label c present).
+ *   qgrp [N], ggrp [M]: int32 group ids, or BOTH null.  Gallery row j is invisible to query i iff
+ *     qgrp != null && qgrp[i] >= 0 && ggrp[j] == qgrp[i]  (self-exclusion: qgrp = ggrp = arange).
+ *   ks [nK]: a HOST array, strictly ascending, 1 <= nK <= 8, ks[0] >= 1, K_max = ks[nK - 1] <= 128.
+ *   rel_mode, with a = qlab[i], b = glab[j]: 0 = any: (a & b) != 0 || (a == 0 && b == 0); 1 = exact: a == b.
+ *   Graded relevance is always Jaccard: J = popcount(a & b) / popcount(a | b), an f64 division; 1.0 when
+ *     a | b == 0.
+ * The list of query i is the first n_i = min(K_max, visible_i) visible gallery rows by descending score,
+ * ties by ascending gallery index.  Outputs:
+ *   idx [N][K_max] int32, score [N][K_max] f32: the list; unfilled places hold idx = -1, score = 0
+ *   filled [N] int32 = n_i;  nrel [N] int32 = R_i, the relevant rows among ALL visible gallery rows
+ *   and per K_a, with m = min(K_a, n_i) and h_r = the relevant rows among the first r places:
+ *   hits [N][nK] int32 = h_m
+ *   ap [N][nK] f64 = (sum_{r = 1..m, rel_r} (double)h_r / (double)r) / (double)min(K_a, R_i), summed in
+ *     ascending r; -1.0 when R_i == 0 or n_i == 0 (such queries are left out of a mean)
+ *   gain [N][nK] f64 = sum_{r = 1..m} J_r in ascending r, NOT divided.
+ * Every float operation has a fixed order and there are no float atomics: the same bits on every run, and a
+ * float64 restatement on idx reproduces ap and gain bit for bit.
+ * ws: ctclip_case_retrieval_ws_bytes(N, M, Dl, K_max) bytes, 16-B aligned (0 = unsupported shape).
+ * 1 <= N, M <= 65536, 1 <= Dl <= 8192, K_max <= 128: CT_ESHAPE otherwise.  A missing required pointer, exactly
+ * one of qgrp / ggrp null, nK outside [1, 8], ks not strictly ascending from >= 1, rel_mode not 0 / 1, or a
+ * short ws: CT_EINVAL.  Non-finite latents are out of scope; the kernels stay inside their buffers on them. */
+int64_t ctclip_case_retrieval_ws_bytes(int32_t N, int32_t M, int32_t Dl, int32_t Kmax);
+int ctclip_case_retrieval(const float* q, const float* g, const int64_t* qlab, const int64_t* glab,
+                          const int32_t* qgrp, const int32_t* ggrp, int32_t N, int32_t M, int32_t Dl,
+                          const int32_t* ks, int32_t nK, int32_t rel_mode, int32_t* idx, float* score,
+                          int32_t* filled, int32_t* nrel, int32_t* hits, double* ap, double* gain, void* ws,
+                          int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- masked language modelling (csrc/mlm.hip)
  * The token-level loss of ct_clip/mlm.py on the text tower: a mask kernel, and a cross-entropy head over the
  * SELECTED rows only (M = B * m_max of the B * L hidden rows); the logits GEMM and the three backward GEMMs
